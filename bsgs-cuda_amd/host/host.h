@@ -1,6 +1,7 @@
 // host.h -- declarations shared by the translation units of bsgs_mi355x, the C++ host of the MI355X BSGS solver (see bsgs_host.cpp for the reference
 // file:line map).  host_config.cpp: command line, limits, checkpoint; host_files.cpp: table files and the CPU-only generator; host_resolver.cpp: dispenser and hit
-// resolver; host_tune.cpp: Tune; host_engines.cpp: per-GPU engines (load, verify, search thread); host_selftest.cpp: -selftest; bsgs_host.cpp: main.
+// resolver; host_jobs.cpp: Job, the key list and its lanes (JobList); host_tune.cpp: Tune; host_engines.cpp: per-GPU engines (load, verify, search thread);
+// host_selftest.cpp: -selftest; bsgs_host.cpp: main and the start-up steps.
 #pragma once
 #include "../../include/bsgs_hip.h"
 #include "../csrc/host_secp.h"
@@ -97,7 +98,7 @@ void cpu_build_g2(const Affine &A, uint32_t t, uint32_t b, uint32_t p, uint8_t *
 
 #define CK(call) do { int rc_ = (call); if (rc_ != BSGS_OK) die(std::string("error " #call "-") + std::to_string(rc_) + ": " + bsgs_last_error()); } while (0)
 
-// ---- shared state (the reference's globals *GlobKey / GlobPub / checker() / quit) ------------------------------
+// ---- run and job state ----------------------------------------------------------------------------------------------
 struct MiniBsgs {
     unsigned mb = 0;
     std::vector<std::pair<uint64_t, uint32_t>> baby;     // (low 64 bits of x(jG), j), j = 1..2^mb, sorted
@@ -117,47 +118,93 @@ struct Tables {
 struct Tile { Scalar key; uint64_t index; };          // counter and dispenser index of a tile: centre = walk_p0 + index * PUBADDBIG
 struct PendingHit { uint32_t code, idx; Tile tile; };
 
-struct Shared {
+// what every job of a run reads and nobody writes once the start-up is over: main() fills it in, everything after the start-up sees it const
+struct Run {
     Config cfg;
     uint64_t maxnonce = 0;
-    double job_tiles = 0.0;                        // tiles in the range of the current job (0 = unbounded / unknown), and the engines that share it
-    int ngpus = 1;
     uint32_t batch_hint = 0;                       // short jobs: tiles per batch (each batch waits for its checker); 0 = a launch per batch
     Scalar center_big, gstep, start, width;      // p*w ; 4*maxnonce*w ; -pk ; pke-pk
-    bool end_range = false, past_end = false;
+    bool end_range = false;
     Affine addpubg, center, pubadd, start_neg;   // -(2w)G ; -(p*w)G ; -(gstep)G ; -(start)G
-    Affine realpub, findpub;
-    std::mutex job_mutex;
-    Scalar glob_key;                              // counter of the next tile to hand out
-    uint64_t glob_index = 0;                      // its index: counter = key0 + index * gstep
-    Affine walk_p0;                               // centre of tile 0 of this job: Q' - key0*G - C*G (1_9_7File.pb:5056-5064)
-    FILE *joblog = nullptr;
-    std::mutex chk_mutex;
-    std::condition_variable chk_cv;
-    std::deque<PendingHit> checker;
+    Tables tab;
+};
+void derive_constants(Run &R);                    // maxnonce, center_big, center, gstep, pubadd, addpubg from cfg (1_9_7File.pb:4689-4712, 4759-4765)
+std::string pub_hex(const Affine &q);             // x || y in hex: how currentwork.txt names a public key
+
+// one public key's search (the reference's globals *GlobKey / GlobPub / checker() / quit): a fresh object per job, seeded completely by its constructor
+struct Job {
+    Job(const Run &run, int listpos, const Affine &realpub, const Affine &findpub, const Scalar &key0, size_t engines, FILE *joblog);
+    const Run &run;
+    const int listpos;
+    const Affine realpub, findpub;
+    const std::string pub_hex;
+    FILE *const joblog;                           // test hook (-joblog): the jobs of lane 0 only
+    const Affine walk_p0;                         // centre of tile 0 of this job: Q' - key0*G - C*G (1_9_7File.pb:5056-5064)
+    std::mutex job_mutex;                         // the dispenser: counter of the next tile to hand out, its index (counter = key0 + index * gstep)
+    Scalar glob_key;
+    uint64_t glob_index = 0;
+    bool past_end = false;
+    std::mutex chk_mutex; std::condition_variable chk_cv; std::deque<PendingHit> checker;      // the checker queue
     std::atomic<bool> quit{false}, all_done{false};
     std::atomic<uint64_t> steps_done{0}, tiles_done{0};
     std::atomic<uint64_t> hits_pushed{0};                   // hits handed to the checker threads
     std::atomic<uint64_t> hits_checked{0}, checker_ns{0};   // resolver load: false positives cost CPU (a small BSGS each with an extended table)
-    std::atomic<int> gpus_finished{0};
-    std::mutex done_mutex;
-    std::condition_variable done_cv;
+    std::atomic<int> gpus_finished{0}; std::mutex done_mutex; std::condition_variable done_cv;
     std::mutex inflight_mutex;
     std::vector<Scalar> inflight;                 // per GPU: counter of the oldest tile it has not finished (checkpoint = min, 1_9_7File.pb:3904-3911)
     std::vector<bool> inflight_valid;
     Scalar winkey;
     bool found = false;
-    Tables *tab = nullptr;
-    int listpos = 1;
-    std::string mainpub_hex;
+    Scalar checkpoint_counter();                  // what currentwork.txt saves for this job: the minimum counter in flight
 };
 
-void save_checkpoint(Shared &S);
-Affine tile_centre(const Shared &S, uint64_t index);
-size_t get_jobs(Shared &S, size_t n, std::vector<Tile> &out, int slot = -1);
+void save_checkpoint(const Config &c, int listpos, const std::string &pub_hex, const Scalar &cnt);
+Affine tile_centre(const Job &J, uint64_t index);
+size_t get_jobs(Job &J, size_t n, std::vector<Tile> &out, int slot = -1);
 int htcpu_lookup_file(int fd, uint64_t ht_items, uint64_t key64, uint32_t *pos, int max);
 int htcpu_lookup(const HostBuf &img, uint64_t ht_items, uint64_t key64, uint32_t *pos, int max);
-void checker_thread(Shared *S);
+void checker_thread(Job *J);
+
+// ---- the list of public keys (-pb / -infile) and its lanes: host_jobs.cpp -------------------------------------------------------------------------
+struct Recovery { bool on = false; int pos = 0; std::string pub, cnt; std::set<int> won; };    // -wl (1_9_7File.pb:4634-4686); won: positions win.txt reports
+Recovery read_recovery(const Config &c);
+std::vector<std::string> read_pubs(const Config &c);
+
+// Hands out list positions to lanes, prints / appends to win.txt in list order, and keeps currentwork.txt naming the oldest job in flight; one mutex guards
+// all of it.  A lane's Job is visible to the other lanes only while it is published: from after its constructor until before its destructor.
+class JobList {
+public:
+    using SaveFn = std::function<void(int listpos, const std::string &pub_hex, const Scalar &cnt)>;
+    struct Claim { int listpos = 0; bool resumed = false; };
+    JobList(std::vector<std::string> pubs, Recovery rec, std::string dir, SaveFn save);
+    size_t size() const { return pubs_.size(); }
+    size_t todo() const;                          // positions from the -wl one on
+    void open_lanes(size_t lanes) { lanes_.assign(lanes, Lane()); live_ = lanes == 1; }     // before the first claim
+    bool live() const { return live_; }           // one lane: a job's lines appear as they happen; several: when its turn in the list comes
+    const Recovery &recovery() const { return rec_; }
+    const std::string &pub(int listpos) const { return pubs_[(size_t)listpos - 1]; }
+    bool claim(size_t lane, Claim &out);          // the next position to search; false when the list is done
+    void publish(size_t lane, Job &J) { std::lock_guard<std::mutex> lk(m_); lanes_[lane].job = &J; }
+    void save_if_oldest(size_t lane);             // the -wt timer: only the oldest job in flight is saved
+    void finish(size_t lane, const std::string &text, bool found, const std::string &win);     // output, withdrawal, checkpoint hand-off
+    int found() const { return found_; }
+private:
+    struct Out { bool done = false, found = false; std::string text, win; };
+    struct Lane { int pos = 0; bool resumed = false; Job *job = nullptr; };     // pos 0: idle; job: once published
+    void emit();
+    void save_lane(const Lane &L);
+    std::mutex m_;
+    const std::vector<std::string> pubs_;
+    const Recovery rec_;
+    bool resume_pending_;                         // the -wl position has not been claimed yet
+    const std::string dir_;
+    const SaveFn save_;
+    std::vector<Out> outs_;
+    std::vector<Lane> lanes_;
+    size_t next_emit_ = 0, next_job_ = 0;
+    int found_ = 0;
+    bool live_ = true;
+};
 
 struct TuneAdvice { double w_log2; uint32_t htsz; bool ext; uint32_t ext_w_log2, ext_htsz; };
 struct TunePlan { double w_log2; uint32_t htsz_arg; bool ext; double build_s, search_s, total_s; uint64_t w; };      // w = the number of baby points itself (it need not be a power of two)
@@ -168,10 +215,10 @@ void tune(int gpu);
 
 bsgs_dev *open_dev(int gpu);
 void print_placement(int gpu, size_t gi, bsgs_dev *dev);
-void load_engines(const Shared &S, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs, const HostBuf &htgpu, const HostBuf &g2);
+void load_engines(const Run &R, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs, const HostBuf &htgpu, const HostBuf &g2);
 void verify_replicas(const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs);
-void verify_tables(const Shared &S, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs);
+void verify_tables(const Run &R, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs);
 void test_corrupt_engine(const std::vector<bsgs_dev *> &devs);       // test build only (-DBSGS_TEST_HOOKS); a no-op in the shipped host
 void per_gpu(const std::vector<int> &gpus, const std::function<void(size_t)> &fn);
-void gpu_thread(Shared *S, int gpu, int slot, bsgs_dev *dev);
+void gpu_thread(Job *J, int gpu, int slot, bsgs_dev *dev);
 int selftest(int argc, char **argv);

@@ -173,24 +173,24 @@ std::string fingerprint(const Config &c)
     s << c.t << c.b << c.p << c.w << c.pk << c.pke << (c.htsz_arg > 31 ? c.htsz_arg : c.htsz);     // Str(t)+Str(b)+Str(p)+Str(w)+pk+pke+Str(htsz)  (4635-4636); a bucket count stands for htsz
     return sha1_hex(s.str());
 }
-void save_checkpoint(Shared &S)
+// the minimum counter over the GPUs' unfinished batches (a restart re-does at most the batches in flight); both locks are
+// held so that a batch cannot leave the dispenser between reading its counter and reading the in-flight table
+Scalar Job::checkpoint_counter()
 {
-    // the minimum counter over the GPUs' unfinished batches (a restart re-does at most the batches in flight); both locks are
-    // held so that a batch cannot leave the dispenser between reading its counter and reading the in-flight table
-    Scalar cnt;
-    {
-        std::lock_guard<std::mutex> lk(S.job_mutex);
-        std::lock_guard<std::mutex> lk2(S.inflight_mutex);
-        cnt = S.glob_key;
-        for (size_t g = 0; g < S.inflight.size(); g++) if (S.inflight_valid[g] && hs::fe_cmp(S.inflight[g], cnt) < 0) cnt = S.inflight[g];
-        if (S.joblog) { fprintf(S.joblog, "save %s\n", hs::fe_to_hex(cnt).c_str()); fflush(S.joblog); }
-    }
-    static std::mutex file_mutex;                                   // several lanes (and a job that has just ended) may save at the same moment
-    std::lock_guard<std::mutex> fl(file_mutex);
-    const std::string tmp = S.cfg.dir + "/currentwork.temp", dst = S.cfg.dir + "/currentwork.txt";
+    std::lock_guard<std::mutex> lk(job_mutex);
+    std::lock_guard<std::mutex> lk2(inflight_mutex);
+    Scalar cnt = glob_key;
+    for (size_t g = 0; g < inflight.size(); g++) if (inflight_valid[g] && hs::fe_cmp(inflight[g], cnt) < 0) cnt = inflight[g];
+    if (joblog) { fprintf(joblog, "save %s\n", hs::fe_to_hex(cnt).c_str()); fflush(joblog); }
+    return cnt;
+}
+// (the product saves only under the JobList's mutex)
+void save_checkpoint(const Config &c, int listpos, const std::string &pub_hex, const Scalar &cnt)
+{
+    const std::string tmp = c.dir + "/currentwork.temp", dst = c.dir + "/currentwork.txt";
     {
         std::ofstream f(tmp, std::ios::binary);
-        f << S.listpos << "\r\n" << S.mainpub_hex << "\r\n" << hs::fe_to_hex(cnt) << "\r\n" << fingerprint(S.cfg) << "\r\n";
+        f << listpos << "\r\n" << pub_hex << "\r\n" << hs::fe_to_hex(cnt) << "\r\n" << fingerprint(c) << "\r\n";
     }
     rename(tmp.c_str(), dst.c_str());
 }

@@ -54,9 +54,9 @@ void per_gpu(const std::vector<int> &gpus, const std::function<void(size_t)> &fn
 //   local      every engine takes / builds its own, concurrently: the reference's shape for file tables, and NO link traffic at all for extended tables (default there);
 //   allgather  extended tables: every engine builds the lines of 1/N of the buckets, then all-gather.
 // Every engine allocates its chain scratch (placed by grade: the reference's cuMemAlloc_v2 before its loop, 1_9_7File.pb:2251) right after its table.
-void load_engines(const Shared &S, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs, const HostBuf &htgpu, const HostBuf &g2)
+void load_engines(const Run &R, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs, const HostBuf &htgpu, const HostBuf &g2)
 {
-    const Config &c = S.cfg;
+    const Config &c = R.cfg;
     const size_t n = devs.size();
     const auto t0 = std::chrono::steady_clock::now();
     auto secs = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
@@ -199,9 +199,9 @@ template <typename F> void parallel_for(size_t n, const F &f)
     for (unsigned q = 0; q < nth; q++) th.emplace_back([&, q]() { for (size_t i = n * q / nth; i < n * (q + 1) / nth; i++) f(i); });
     for (auto &t : th) t.join();
 }
-Samples make_samples(const Shared &S)
+Samples make_samples(const Run &R)
 {
-    const Config &c = S.cfg;
+    const Config &c = R.cfg;
     Samples m;
     uint64_t seed = 0xB5650000ull ^ c.w ^ ((uint64_t)c.htsz_arg << 40);
     const size_t NIN = 1024, NOUT = 256, NG = 1024;
@@ -213,21 +213,21 @@ Samples make_samples(const Shared &S)
     while (m.k.size() < m.n_in + NOUT) m.k.push_back(c.w + 1 + splitmix(seed) % c.w);
     m.key64.resize(m.k.size());
     parallel_for(m.k.size(), [&](size_t i) { m.key64[i] = hs::point_mul(hs::G, hs::sc_from_u128((hs::u128)m.k[i])).x.l[0]; });
-    m.gi = {0, S.maxnonce - 1};
-    if (S.maxnonce > 2) m.gi.push_back(1);
-    while (m.gi.size() < NG) m.gi.push_back(splitmix(seed) % S.maxnonce);
+    m.gi = {0, R.maxnonce - 1};
+    if (R.maxnonce > 2) m.gi.push_back(1);
+    while (m.gi.size() < NG) m.gi.push_back(splitmix(seed) % R.maxnonce);
     m.giant.resize(m.gi.size());
-    parallel_for(m.gi.size(), [&](size_t i) { m.giant[i] = hs::point_mul(S.addpubg, hs::fe_from_u64(m.gi[i] + 1)); });
+    parallel_for(m.gi.size(), [&](size_t i) { m.giant[i] = hs::point_mul(R.addpubg, hs::fe_from_u64(m.gi[i] + 1)); });
     return m;
 }
 }  // namespace
 
-void verify_tables(const Shared &S, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs)
+void verify_tables(const Run &R, const std::vector<int> &gpus, const std::vector<bsgs_dev *> &devs)
 {
-    const Config &c = S.cfg;
+    const Config &c = R.cfg;
     const auto t0 = std::chrono::steady_clock::now();
     auto secs = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-    const Samples m = make_samples(S);
+    const Samples m = make_samples(R);
     const double t_samples = secs();
     // htCPU: the image the resolver will use must hold position k - 1 for every sampled k (checkHTpackFile 1_9_7File.pb:3101-3134)
     if (!c.ext) {
@@ -236,14 +236,14 @@ void verify_tables(const Shared &S, const std::vector<int> &gpus, const std::vec
         std::atomic<uint64_t> first_bad{0};
         parallel_for(m.n_in, [&](size_t i) {
             uint32_t pos[64];
-            const int np = S.tab->htcpu_fd >= 0 ? htcpu_lookup_file(S.tab->htcpu_fd, items, m.key64[i], pos, 64) : htcpu_lookup(S.tab->htcpu, items, m.key64[i], pos, 64);
+            const int np = R.tab.htcpu_fd >= 0 ? htcpu_lookup_file(R.tab.htcpu_fd, items, m.key64[i], pos, 64) : htcpu_lookup(R.tab.htcpu, items, m.key64[i], pos, 64);
             bool ok = false;
             for (int q = 0; q < std::min(np, 64); q++) ok |= (uint64_t)pos[q] + 1 == m.k[i];
             if (!ok && !bad.fetch_add(1)) first_bad = m.k[i];
         });
         if (bad.load()) die("table verification FAILED: htCPU does not hold position k - 1 for " + std::to_string(bad.load()) + " of " + std::to_string(m.n_in) +
                             " sampled k (first: k = " + std::to_string(first_bad.load()) + "): the HT files do not belong to -w " + std::to_string(c.w) + " or are damaged");
-        printf("Table verification: htCPU (%s) holds position k - 1 for %zu of %zu sampled k*G\n", S.tab->htcpu_fd >= 0 ? "file" : "RAM", m.n_in, m.n_in);
+        printf("Table verification: htCPU (%s) holds position k - 1 for %zu of %zu sampled k*G\n", R.tab.htcpu_fd >= 0 ? "file" : "RAM", m.n_in, m.n_in);
     }
     std::vector<std::string> lines(devs.size()), errors(devs.size());
     per_gpu(gpus, [&](size_t gi) {
@@ -287,7 +287,7 @@ void verify_tables(const Shared &S, const std::vector<int> &gpus, const std::vec
     printf("[startup] %-44s %.3fs (samples on the host %.3fs)\n", "table + giants verification", secs(), t_samples);
 }
 
-void gpu_thread(Shared *S, int gpu, int slot, bsgs_dev *dev)
+void gpu_thread(Job *J, int gpu, int slot, bsgs_dev *dev)
 {
     uint32_t tpl = 48;
     if (bsgs_tiles_per_launch(dev, &tpl) != BSGS_OK || !tpl) tpl = 48;
@@ -296,34 +296,34 @@ void gpu_thread(Shared *S, int gpu, int slot, bsgs_dev *dev)
     // hit (1_9_7File.pb:2442-2523) -- so such a job is dealt in about six batches per GPU (not below 16 tiles: the narrow batchings keep small launches at
     // 36-38 G): with the key anywhere in the range 0.6 of the work is done on average instead of all of it.
     size_t batch = tpl;
-    const bool wait_for_checker = S->batch_hint != 0;
-    if (S->batch_hint) batch = std::min<size_t>(S->batch_hint, tpl);
+    const bool wait_for_checker = J->run.batch_hint != 0;
+    if (J->run.batch_hint) batch = std::min<size_t>(J->run.batch_hint, tpl);
     std::vector<Tile> tiles;
     std::vector<uint8_t> centres;
     std::vector<bsgs_hit_ex> hits(65536);
     auto push_hits = [&](const bsgs_hit_ex *h, uint32_t n, const Tile *base) {
         if (!n) return;
-        std::lock_guard<std::mutex> lk(S->chk_mutex);
-        for (uint32_t i = 0; i < n; i++) S->checker.push_back({h[i].code, h[i].idx, base[h[i].tile]});
-        S->hits_pushed += n;
-        S->chk_cv.notify_all();
+        std::lock_guard<std::mutex> lk(J->chk_mutex);
+        for (uint32_t i = 0; i < n; i++) J->checker.push_back({h[i].code, h[i].idx, base[h[i].tile]});
+        J->hits_pushed += n;
+        J->chk_cv.notify_all();
     };
     // tiles [i0, i0 + n) of the current batch with centres added on the host and uploaded (the reference's way: -hostcentres, and the
     // fallback when the device walk meets the point at infinity)
     auto run_host_centres = [&](size_t i0, size_t n, uint32_t *nh) {
         centres.resize(n * 64);
         for (size_t i = 0; i < n; i++) {
-            const Affine c = tile_centre(*S, tiles[i0 + i].index);
+            const Affine c = tile_centre(*J, tiles[i0 + i].index);
             if (c.inf) die("tile centre is the point at infinity (the public key equals -(counter + p*w)*G): the reference cannot search this tile either");
             hs::affine_to_le(c, &centres[i * 64], &centres[i * 64 + 32]);
         }
         return bsgs_run(dev, centres.data(), (uint32_t)n, hits.data(), (uint32_t)hits.size(), nh, nullptr);
     };
-    while (!S->quit.load()) {
-        const size_t n = get_jobs(*S, batch, tiles, slot);
+    while (!J->quit.load()) {
+        const size_t n = get_jobs(*J, batch, tiles, slot);
         if (!n) break;                                            // end of space for this GPU
         uint32_t nh = 0;
-        int rc = S->cfg.host_centres ? run_host_centres(0, n, &nh)
+        int rc = J->run.cfg.host_centres ? run_host_centres(0, n, &nh)
                                      : bsgs_run_walk(dev, tiles[0].index, (uint32_t)n, hits.data(), (uint32_t)hits.size(), &nh, nullptr);
         if (rc == BSGS_ERR_DEGENERATE) rc = run_host_centres(0, n, &nh);
         if (rc == BSGS_ERR_OVERFLOW) {
@@ -332,25 +332,25 @@ void gpu_thread(Shared *S, int gpu, int slot, bsgs_dev *dev)
             fprintf(stderr, "\nGPU#%d: %u hits in one batch of %zu tiles exceed the hit buffer; re-running tile by tile\n", gpu, nh, n);
             for (size_t i = 0; i < n; i++) {
                 uint32_t n1 = 0;
-                int r1 = S->cfg.host_centres ? run_host_centres(i, 1, &n1) : bsgs_run_walk(dev, tiles[i].index, 1, hits.data(), (uint32_t)hits.size(), &n1, nullptr);
+                int r1 = J->run.cfg.host_centres ? run_host_centres(i, 1, &n1) : bsgs_run_walk(dev, tiles[i].index, 1, hits.data(), (uint32_t)hits.size(), &n1, nullptr);
                 if (r1 == BSGS_ERR_DEGENERATE) r1 = run_host_centres(i, 1, &n1);
                 if (r1 != BSGS_OK) die(std::string("error bsgs_run-") + std::to_string(r1) + ": " + bsgs_last_error() + " (one tile alone overflows the hit buffer: raise -htsz)");
                 push_hits(hits.data(), n1, &tiles[i]);
             }
         } else if (rc != BSGS_OK) die(std::string("error bsgs_run-") + std::to_string(rc) + ": " + bsgs_last_error());
         else push_hits(hits.data(), nh, tiles.data());
-        S->steps_done += 2 * S->maxnonce * n;
-        S->tiles_done += n;
+        J->steps_done += 2 * J->run.maxnonce * n;
+        J->tiles_done += n;
         // a short job (batches smaller than a launch: see above) does not run ahead of its checker: the next batch is dispensed once this one's hits are resolved
         // (microseconds each with the htCPU table), so that the batch that holds the key is the last one
-        if (wait_for_checker) while (!S->quit.load() && S->hits_checked.load() < S->hits_pushed.load()) std::this_thread::sleep_for(std::chrono::microseconds(20));
+        if (wait_for_checker) while (!J->quit.load() && J->hits_checked.load() < J->hits_pushed.load()) std::this_thread::sleep_for(std::chrono::microseconds(20));
         {
-            std::lock_guard<std::mutex> lk(S->inflight_mutex);
-            S->inflight_valid[slot] = false;
-            if (S->joblog) { fprintf(S->joblog, "done %d %llu %zu\n", slot, (unsigned long long)tiles[0].index, n); fflush(S->joblog); }
+            std::lock_guard<std::mutex> lk(J->inflight_mutex);
+            J->inflight_valid[slot] = false;
+            if (J->joblog) { fprintf(J->joblog, "done %d %llu %zu\n", slot, (unsigned long long)tiles[0].index, n); fflush(J->joblog); }
         }
     }
     printf("GPU#%d job finished\n", gpu);
-    { std::lock_guard<std::mutex> lk(S->done_mutex); S->gpus_finished++; }
-    S->done_cv.notify_all();
+    { std::lock_guard<std::mutex> lk(J->done_mutex); J->gpus_finished++; }
+    J->done_cv.notify_all();
 }

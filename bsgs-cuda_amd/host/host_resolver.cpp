@@ -3,38 +3,38 @@
 #include "host.h"
 
 // centre of tile `index`: P0 + index * PUBADDBIG (what GetJob accumulates one addition at a time, 1_9_7File.pb:2077-2092)
-Affine tile_centre(const Shared &S, uint64_t index)
+Affine tile_centre(const Job &J, uint64_t index)
 {
-    if (!index) return S.walk_p0;
-    return hs::point_add(S.walk_p0, hs::point_mul(S.pubadd, hs::fe_from_u64(index)));
+    if (!index) return J.walk_p0;
+    return hs::point_add(J.walk_p0, hs::point_mul(J.run.pubadd, hs::fe_from_u64(index)));
 }
 
 // GetJob for a batch: hand out `n` consecutive tiles (1_9_7File.pb:2077-2092).  Only the COUNTER advances on the host; the
 // centres are derived on the GPU from the tile index (bsgs_enqueue_walk), or by tile_centre() under -hostcentres.
-size_t get_jobs(Shared &S, size_t n, std::vector<Tile> &out, int slot)
+size_t get_jobs(Job &J, size_t n, std::vector<Tile> &out, int slot)
 {
-    std::lock_guard<std::mutex> lk(S.job_mutex);
+    std::lock_guard<std::mutex> lk(J.job_mutex);
     out.clear();
-    Scalar key = S.glob_key;
-    uint64_t index = S.glob_index;
+    Scalar key = J.glob_key;
+    uint64_t index = J.glob_index;
     for (size_t i = 0; i < n; i++) {
         // 1_9_7File.pb:2512-2518 tests the counter AFTER the launch: the first tile whose counter exceeds the width is still
         // searched (a tile reaches 2w*maxnonce - p*w below its counter), then the dispenser closes
-        if (S.past_end) break;
-        if (S.end_range && hs::fe_cmp(key, S.width) > 0) S.past_end = true;
-        if (S.cfg.max_tiles && S.tiles_done.load() + out.size() >= S.cfg.max_tiles) break;
+        if (J.past_end) break;
+        if (J.run.end_range && hs::fe_cmp(key, J.run.width) > 0) J.past_end = true;
+        if (J.run.cfg.max_tiles && J.tiles_done.load() + out.size() >= J.run.cfg.max_tiles) break;
         Tile t; t.key = key; t.index = index;
         out.push_back(t);
-        key = hs::sc_add(key, S.gstep);
+        key = hs::sc_add(key, J.run.gstep);
         index++;
     }
     if (out.empty()) return 0;
-    S.glob_key = key;
-    S.glob_index = index;
+    J.glob_key = key;
+    J.glob_index = index;
     if (slot >= 0) {   // the batch is in flight from the moment it leaves the dispenser (checkpoint = min over GPUs, 1_9_7File.pb:3904-3911)
-        std::lock_guard<std::mutex> lk2(S.inflight_mutex);
-        S.inflight[slot] = out[0].key; S.inflight_valid[slot] = true;
-        if (S.joblog) { fprintf(S.joblog, "take %d %llu %zu %s\n", slot, (unsigned long long)out[0].index, out.size(), hs::fe_to_hex(out[0].key).c_str()); fflush(S.joblog); }
+        std::lock_guard<std::mutex> lk2(J.inflight_mutex);
+        J.inflight[slot] = out[0].key; J.inflight_valid[slot] = true;
+        if (J.joblog) { fprintf(J.joblog, "take %d %llu %zu %s\n", slot, (unsigned long long)out[0].index, out.size(), hs::fe_to_hex(out[0].key).c_str()); fflush(J.joblog); }
     }
     return out.size();
 }
@@ -138,40 +138,40 @@ std::vector<uint64_t> MiniBsgs::find(const Affine &T, uint64_t w) const
     return out;
 }
 
-bool try_key(const Shared &S, const Scalar &kprime, Scalar &key_out)
+bool try_key(const Job &J, const Scalar &kprime, Scalar &key_out)
 {
     const Affine tp = hs::point_mul(hs::G, kprime);
-    if (tp.inf || !hs::fe_equal(tp.x, S.findpub.x) || !hs::fe_equal(tp.y, S.findpub.y)) return false;
-    const Scalar key = hs::sc_add(kprime, S.start);
+    if (tp.inf || !hs::fe_equal(tp.x, J.findpub.x) || !hs::fe_equal(tp.y, J.findpub.y)) return false;
+    const Scalar key = hs::sc_add(kprime, J.run.start);
     const Affine rp = hs::point_mul(hs::G, key);
-    if (rp.inf || !hs::fe_equal(rp.x, S.realpub.x) || !hs::fe_equal(rp.y, S.realpub.y)) return false;
+    if (rp.inf || !hs::fe_equal(rp.x, J.realpub.x) || !hs::fe_equal(rp.y, J.realpub.y)) return false;
     key_out = key;
     return true;
 }
 
-bool resolve_hit(const Shared &S, const PendingHit &hit, Scalar &key_out)
+bool resolve_hit(const Job &J, const PendingHit &hit, Scalar &key_out)
 {
     // k' = cnt + C + e1*(idx+1)*2w + e2*b'   (all sign pairs are verified by scalar multiplication)
-    const Scalar base = hs::sc_add(hit.tile.key, S.center_big);
-    const Scalar two_w = hs::sc_from_u128((hs::u128)S.cfg.w * 2);
+    const Scalar base = hs::sc_add(hit.tile.key, J.run.center_big);
+    const Scalar two_w = hs::sc_from_u128((hs::u128)J.run.cfg.w * 2);
     const Scalar g = hit.code == 5 ? hs::fe_from_u64(0) : hs::sc_mul_small(two_w, (uint64_t)hit.idx + 1);
     if (hit.code == 4) {
-        Scalar k = hs::sc_add(base, g); if (try_key(S, k, key_out)) return true;
-        k = hs::sc_sub(base, g); return try_key(S, k, key_out);
+        Scalar k = hs::sc_add(base, g); if (try_key(J, k, key_out)) return true;
+        k = hs::sc_sub(base, g); return try_key(J, k, key_out);
     }
-    const Affine centre = tile_centre(S, hit.tile.index);
+    const Affine centre = tile_centre(J, hit.tile.index);
     Affine T = centre;
     if (hit.code != 5) {
-        Affine gi = hs::point_mul(S.addpubg, hs::fe_from_u64((uint64_t)hit.idx + 1));
+        Affine gi = hs::point_mul(J.run.addpubg, hs::fe_from_u64((uint64_t)hit.idx + 1));
         if (hit.code == 2) gi = hs::affine_neg(gi);
         T = hs::point_add(centre, gi);
         if (T.inf) return false;
     }
     std::vector<uint64_t> babies;                 // b' with x(b'G) = x(T) as far as the table knows
-    if (S.cfg.ext) babies = S.tab->mini.find(T, S.cfg.w);
+    if (J.run.cfg.ext) babies = J.run.tab.mini.find(T, J.run.cfg.w);
     else {
         uint32_t pos[64];
-        int np = S.tab->htcpu_fd >= 0 ? htcpu_lookup_file(S.tab->htcpu_fd, 1ull << S.cfg.htsz, T.x.l[0], pos, 64) : htcpu_lookup(S.tab->htcpu, 1ull << S.cfg.htsz, T.x.l[0], pos, 64);
+        int np = J.run.tab.htcpu_fd >= 0 ? htcpu_lookup_file(J.run.tab.htcpu_fd, 1ull << J.run.cfg.htsz, T.x.l[0], pos, 64) : htcpu_lookup(J.run.tab.htcpu, 1ull << J.run.cfg.htsz, T.x.l[0], pos, 64);
         for (int q = 0; q < std::min(np, 64); q++) babies.push_back((uint64_t)pos[q] + 1);
     }
     for (uint64_t bprime : babies) {
@@ -180,34 +180,34 @@ bool resolve_hit(const Shared &S, const PendingHit &hit, Scalar &key_out)
             Scalar e1g;
             if (hit.code == 5) { if (s1) break; e1g = base; }
             else e1g = ((hit.code == 1) ^ (s1 == 1)) ? hs::sc_add(base, g) : hs::sc_sub(base, g);
-            Scalar k = hs::sc_add(e1g, bb); if (try_key(S, k, key_out)) return true;
-            k = hs::sc_sub(e1g, bb); if (try_key(S, k, key_out)) return true;
+            Scalar k = hs::sc_add(e1g, bb); if (try_key(J, k, key_out)) return true;
+            k = hs::sc_sub(e1g, bb); if (try_key(J, k, key_out)) return true;
         }
     }
     return false;
 }
 
-void checker_thread(Shared *S)
+void checker_thread(Job *J)
 {
     for (;;) {
         PendingHit hit;
         {
-            std::unique_lock<std::mutex> lk(S->chk_mutex);
-            S->chk_cv.wait(lk, [&] { return !S->checker.empty() || S->all_done.load(); });
-            if (S->checker.empty()) return;
-            hit = S->checker.front();
-            S->checker.pop_front();
+            std::unique_lock<std::mutex> lk(J->chk_mutex);
+            J->chk_cv.wait(lk, [&] { return !J->checker.empty() || J->all_done.load(); });
+            if (J->checker.empty()) return;
+            hit = J->checker.front();
+            J->checker.pop_front();
         }
-        if (S->quit.load()) continue;
+        if (J->quit.load()) continue;
         Scalar key;
         const auto tc0 = std::chrono::steady_clock::now();
-        const bool solved = resolve_hit(*S, hit, key);
-        S->checker_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tc0).count();
+        const bool solved = resolve_hit(*J, hit, key);
+        J->checker_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tc0).count();
         if (solved) {
-            std::lock_guard<std::mutex> lk(S->chk_mutex);
-            S->winkey = key; S->found = true;
-            S->quit.store(true);
+            std::lock_guard<std::mutex> lk(J->chk_mutex);
+            J->winkey = key; J->found = true;
+            J->quit.store(true);
         }
-        S->hits_checked++;                      // after `quit`: a driver thread that waits for its hits to be resolved (short jobs) sees the verdict with the count
+        J->hits_checked++;                      // after `quit`: a driver thread that waits for its hits to be resolved (short jobs) sees the verdict with the count
     }
 }

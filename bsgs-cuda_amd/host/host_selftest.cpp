@@ -1,6 +1,54 @@
 // host_selftest.cpp -- -selftest: the host-side logic that needs no GPU (CPU test tier, tests/test_host_logic.py).
 #include "host.h"
 
+// JobList driven by a script, no GPU and no threads: N [wl=POS:HEXCNT] [won=P,P...] then events c<lane> (claim), p<lane> (publish: a Job of the claimed key
+// seeded from its start counter), t<lane> (the published job dispenses 3 tiles and finishes them), f<lane> (finish).  Keys are 1*G .. N*G, two lanes.
+// Prints "claim <lane> <pos> <resumed>" / "claim <lane> none", "emit <pos>" in the order the list emits, "save <pos> <pubkey> <counter>" for every checkpoint.
+static int selftest_joblist(const std::vector<std::string> &a)
+{
+    const int n = atoi(a[0].c_str());
+    Recovery rec;
+    std::vector<std::string> pubs;
+    for (int k = 1; k <= n; k++) pubs.push_back(pub_hex(hs::point_mul(hs::G, hs::fe_from_u64((uint64_t)k))));
+    Run R;
+    R.cfg.t = 64; R.cfg.b = 8; R.cfg.p = 16; R.cfg.w = 65536;
+    derive_constants(R);
+    size_t e = 1;
+    for (; e < a.size() && a[e].find('=') != std::string::npos; e++) {
+        const std::string v = a[e].substr(a[e].find('=') + 1);
+        if (a[e].rfind("wl=", 0) == 0) { rec.on = true; rec.pos = atoi(v.c_str()); rec.cnt = v.substr(v.find(':') + 1); if (rec.pos < 1 || rec.pos > n) return 2; rec.pub = pubs[(size_t)rec.pos - 1]; }
+        else if (a[e].rfind("won=", 0) == 0) { std::stringstream ss(v); std::string tok; while (std::getline(ss, tok, ',')) rec.won.insert(atoi(tok.c_str())); }
+        else return 2;
+    }
+    JobList jobs(pubs, rec, "/nonexistent", [](int pos, const std::string &pub, const Scalar &cnt) { printf("save %d %s %s\n", pos, pub.c_str(), hs::fe_to_hex(cnt).c_str()); });
+    jobs.open_lanes(2);
+    JobList::Claim claimed[2];
+    std::unique_ptr<Job> job[2];
+    for (; e < a.size(); e++) {
+        const char ev = a[e][0];
+        const size_t l = (size_t)atoi(a[e].c_str() + 1);
+        if (a[e].size() != 2 || l > 1 || (ev == 'c') == (claimed[l].listpos > 0) || (ev == 't' && !job[l])) return 2;      // (a script the list would never see)
+        if (ev == 'c') {
+            if (!jobs.claim(l, claimed[l])) { claimed[l] = JobList::Claim(); printf("claim %zu none\n", l); }
+            else printf("claim %zu %d %d\n", l, claimed[l].listpos, claimed[l].resumed ? 1 : 0);
+        } else if (ev == 'p') {
+            Affine q; hs::parse_pubkey(q, jobs.pub(claimed[l].listpos));
+            Scalar key0 = hs::fe_from_u64(1);
+            if (claimed[l].resumed) hs::fe_from_hex(key0, rec.cnt);
+            job[l].reset(new Job(R, claimed[l].listpos, q, q, key0, 1, nullptr));
+            jobs.publish(l, *job[l]);
+        } else if (ev == 't') {
+            std::vector<Tile> tiles;
+            get_jobs(*job[l], 3, tiles, 0);
+            job[l]->inflight_valid[0] = false;
+        } else if (ev == 'f') {
+            jobs.finish(l, "emit " + std::to_string(claimed[l].listpos) + "\n", false, "");
+            job[l].reset(); claimed[l] = JobList::Claim();
+        } else return 2;
+    }
+    return 0;
+}
+
 // ---- -selftest: the host-side logic that needs no GPU (CPU test tier, tests/test_host_logic.py) ------------------------
 // prints "key value" lines: SHA1, the configuration fingerprint, host EC arithmetic, public-key parsing, the dispenser
 // sequence and the table-free resolver, each for the inputs given on the command line
@@ -25,22 +73,17 @@ int selftest(int argc, char **argv)
             const std::vector<Affine> v = hs::multiples(hs::point_mul(hs::G, k), n);
             printf("multiples %s\n", pt(v.back()).c_str());
         } else if (a[i] == "jobs" && i + 5 < a.size()) {                     // dispenser: t b p w n -> counters and centres of n tiles
-            Shared S;
-            S.cfg.t = (uint32_t)atoi(a[i + 1].c_str()); S.cfg.b = (uint32_t)atoi(a[i + 2].c_str()); S.cfg.p = (uint32_t)atoi(a[i + 3].c_str());
-            S.cfg.w = strtoull(a[i + 4].c_str(), nullptr, 10);
+            Run R;
+            R.cfg.t = (uint32_t)atoi(a[i + 1].c_str()); R.cfg.b = (uint32_t)atoi(a[i + 2].c_str()); R.cfg.p = (uint32_t)atoi(a[i + 3].c_str());
+            R.cfg.w = strtoull(a[i + 4].c_str(), nullptr, 10);
             const size_t n = (size_t)atoi(a[i + 5].c_str());
             Affine pub; if (!hs::parse_pubkey(pub, cut_hex(a[i + 6])) ) return 2;
             i += 6;
-            S.maxnonce = (uint64_t)S.cfg.t * S.cfg.b * S.cfg.p;
-            S.center_big = hs::sc_from_u128((hs::u128)S.cfg.p * S.cfg.w);
-            S.center = hs::affine_neg(hs::point_mul(hs::G, S.center_big));
-            S.gstep = hs::sc_mul_small(hs::sc_from_u128((hs::u128)S.maxnonce * S.cfg.w), 4);
-            S.pubadd = hs::affine_neg(hs::point_mul(hs::G, S.gstep));
-            S.glob_key = hs::fe_from_u64(1); S.glob_index = 0;
-            S.walk_p0 = hs::point_add(hs::point_add(pub, hs::affine_neg(hs::point_mul(hs::G, S.glob_key))), S.center);
+            derive_constants(R);
+            Job J(R, 1, pub, pub, hs::fe_from_u64(1), 0, nullptr);
             std::vector<Tile> tiles;
-            get_jobs(S, n, tiles);
-            for (const Tile &t : tiles) printf("job %s %s\n", hs::fe_to_hex(t.key).c_str(), pt(tile_centre(S, t.index)).c_str());
+            get_jobs(J, n, tiles);
+            for (const Tile &t : tiles) printf("job %s %s\n", hs::fe_to_hex(t.key).c_str(), pt(tile_centre(J, t.index)).c_str());
         } else if (a[i] == "minibsgs" && i + 2 < a.size()) {                 // w (decimal), then hex scalars m: all b' <= w with x(b'G) = x(mG)
             const uint64_t w = strtoull(a[++i].c_str(), nullptr, 10);
             MiniBsgs mb; mb.build(w, 4);
@@ -80,16 +123,20 @@ int selftest(int argc, char **argv)
             i += 2;
             printf("limits %s\n", m.empty() ? "ok" : m == " " ? "exit" : m.c_str());
         } else if (a[i] == "checkpoint" && i + 1 < a.size()) {                // next counter, then in-flight counters ("-" = idle GPU): the saved one
-            Shared S;
-            if (!hs::fe_from_hex(S.glob_key, a[++i])) return 2;
+            Run R;
+            R.cfg.dir = "/tmp";
+            Scalar next;
+            if (!hs::fe_from_hex(next, a[++i])) return 2;
+            Job J(R, 1, hs::G, hs::G, next, 0, stdout);
             for (++i; i < a.size(); i++) {
                 Scalar v = hs::fe_from_u64(0);
                 const bool valid = a[i] != "-";
                 if (valid && !hs::fe_from_hex(v, a[i])) return 2;
-                S.inflight.push_back(v); S.inflight_valid.push_back(valid);
+                J.inflight.push_back(v); J.inflight_valid.push_back(valid);
             }
-            S.cfg.dir = "/tmp"; S.mainpub_hex = "selftest"; S.joblog = stdout;
-            save_checkpoint(S);
+            save_checkpoint(R.cfg, J.listpos, "selftest", J.checkpoint_counter());
+        } else if (a[i] == "joblist" && i + 1 < a.size()) {                  // the rest of the command line is the script
+            return selftest_joblist(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else { fprintf(stderr, "selftest: unknown item %s\n", a[i].c_str()); return 2; }
     }
     return 0;

@@ -142,6 +142,42 @@ def test_checkpoint_is_the_minimum_in_flight_counter():
     assert selftest("checkpoint", "0901", "0a01", "0b01")[0] == ["save", "%064x" % 0x901]
 
 
+def test_job_list_skips_resumes_emits_in_order_and_checkpoints_the_oldest_job():
+    """JobList (host/host_jobs.cpp) on two lanes, driven by claim / publish / take-3-tiles / finish events (keys k*G, k = list position): positions before -wl
+    and positions win.txt reports are skipped, the -wl position resumes from the saved counter, output keeps list order when lane 1 finishes first, and when a
+    job ends currentwork.txt names the oldest position still in flight (claimed but not yet published: from its start counter) or, with none in flight, the
+    next position from counter 1"""
+    from pybsgs import ecpy
+    gstep = 4 * 64 * 8 * 16 * 65536                              # the script's Run: -t 64 -b 8 -p 16 -w 65536
+
+    def save(pos, cnt):
+        return ["save", str(pos), "%064x%064x" % ecpy.mul(pos), "%064x" % cnt]
+
+    def claim(lane, pos, resumed=0):
+        return ["claim", str(lane), str(pos), str(resumed)]
+
+    out = selftest("joblist", 5, "c0", "c1", "p0", "p1", "t0", "t1", "t1", "f1", "c1", "f0", "p1", "f1", "c0", "c1", "p0", "p1", "f0", "f1", "c0")
+    assert out == [claim(0, 1), claim(1, 2),
+                   save(1, 1 + 3 * gstep),                        # position 2 ends first: nothing emitted yet; position 1 is in flight, 3 tiles done
+                   claim(1, 3),
+                   ["emit", "1"], ["emit", "2"], save(3, 1),      # position 3 is claimed, not yet published: from its start
+                   ["emit", "3"], save(4, 1),                     # nothing in flight: the next position
+                   claim(0, 4), claim(1, 5),
+                   ["emit", "4"], save(5, 1), ["emit", "5"],      # after the last position: nothing left to name
+                   ["claim", "0", "none"]]
+
+    out = selftest("joblist", 6, "wl=3:abc", "won=4", "c0", "c1", "f1", "c1", "p0", "t0", "p1", "f1", "f0", "c0")
+    assert out == [claim(0, 3, 1), claim(1, 5),                   # 1, 2 lie before the -wl position, 4 is in win.txt
+                   save(3, 0xABC),                                # resumed, not yet published: the saved counter
+                   claim(1, 6),
+                   save(3, 0xABC + 3 * gstep),                    # published: its own counter
+                   ["emit", "3"], ["emit", "5"], ["emit", "6"],
+                   ["claim", "0", "none"]]
+
+    # the -wl position is reported in win.txt already: the saved counter belongs to a finished job, nothing resumes
+    assert selftest("joblist", 4, "wl=2:abc", "won=2", "c0", "c1") == [claim(0, 3), claim(1, 4)]
+
+
 def test_reference_table_limits_and_unsafe_question():
     """the reference's limits on -w / -htsz for tables in its format and its UNSAFE-mode question (1_9_7File.pb:4412-4472): -w below 3069485951, -htsz below 32,
     "type Y" above the per--htsz duplicate limits (27: 1331331443, 28: 1777178603), and the "-htsz parametr is to low" warning (log2(w) - htsz > 3)."""
