@@ -124,6 +124,11 @@ extern "C" int bsgs_dev_open(int device_id, bsgs_dev **out)
         if (k != 13 && k != 10 && k != 0) { delete d; return fail(BSGS_ERR_ARG, "BSGS_KERNEL_VARIANT=%d: this library has 13 (default), 10 and 0", k); }
         d->variant = k;
     }
+    if (const char *v = getenv("BSGS_TILES_PER_BLOCK")) {                         // A-B and tests: 1 = one tile per block of the tile kernel, 2 = two where the launch allows it (default)
+        const int k = atoi(v);
+        if (k != 1 && k != 2) { delete d; return fail(BSGS_ERR_ARG, "BSGS_TILES_PER_BLOCK=%d: 1 or 2", k); }
+        d->tiles_per_block = (uint32_t)k;
+    }
     HIPCHK(hipGetDeviceProperties(&d->prop, device_id));
     HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&d->ev0));
@@ -260,6 +265,14 @@ extern "C" int bsgs_debug_last_batching(bsgs_dev *d, uint32_t *threads, uint32_t
     if (!d) return fail(BSGS_ERR_ARG, "null");
     if (threads) *threads = d->last_Ti;
     if (giants_per_thread) *giants_per_thread = d->last_pi;
+    return BSGS_OK;
+}
+
+// tiles per block of the most recent tile launch (1, or 2 for the pair walk of the quad-chain kernels: launch_tiles)
+extern "C" int bsgs_debug_last_tiles_per_block(bsgs_dev *d, uint32_t *tiles)
+{
+    if (!d || !tiles) return fail(BSGS_ERR_ARG, "null");
+    *tiles = d->last_tpb;
     return BSGS_OK;
 }
 
@@ -571,8 +584,14 @@ static int launch_tiles(bsgs_dev *d, const fe *centres_dev, uint32_t ntiles, uin
                            (const u32 *)d->quirk_list, (u32)d->quirk_host.size());
         HIPCHK(hipGetLastError());
     }
-    const dim3 grid((unsigned)(((Ti + bs - 1) / bs) * ntiles)), block(bs);
     const uint32_t group = bsgs_chain_group(d, pi);
+    // two tiles per block (giant_kernel.hip.h tile_pair_walk): the quad-chain kernels of 64-byte lines, an even number of tiles with the default batching, and both
+    // tiles of a pair in one scratch buffer or piece (pieces of one tile cannot hold a pair).  Narrow launches keep one tile per block: they need the blocks.
+    const bool pair = d->tiles_per_block == 2 && group == 4 && !nb && (ntiles & 1u) == 0 && d->layout == BSGS_TABLE_LINES64 &&
+                      (d->chain_pieces.empty() || d->chain_piece_log >= 1);
+    A.tiles_per_block = pair ? 2u : 1u;
+    d->last_tpb = A.tiles_per_block;
+    const dim3 grid((unsigned)(((Ti + bs - 1) / bs) * (ntiles / A.tiles_per_block))), block(bs);
     // chained kernel, per wave: two probe slots (QUAD: one probe slot + the two 2 KiB temporaries) + the 2 KiB S stash: 4 blocks fill the 160 KiB of a CU exactly
     const bool l128 = d->layout == BSGS_TABLE_LINES128;
     const size_t slot = l128 ? 8192 : 4096;

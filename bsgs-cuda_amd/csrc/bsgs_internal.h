@@ -53,6 +53,8 @@ struct bsgs_dev {
     bool narrow_off = false;               // this geometry's narrow copies did not fit once (reset by set_geometry / a table change)
     bool narrow_env_off = false;           // BSGS_NARROW_LAUNCHES=0
     uint32_t last_Ti = 0, last_pi = 0;     // batching of the last tile launch (bsgs_debug_last_batching)
+    uint32_t tiles_per_block = 2;          // BSGS_TILES_PER_BLOCK: 2 = two tiles per block of the quad-chain kernel where a launch allows it (launch_tiles), 1 = never
+    uint32_t last_tpb = 1;                 // tiles per block of the last tile launch (bsgs_debug_last_tiles_per_block)
     u32x4 *chain = nullptr;     // one-buffer scratch: [tile][p][2][T] (per-giant kernel) or the chained kernel's layout when not in pieces
     u32 *csr = nullptr;         // htGPU image
     bool csr_owned = true;

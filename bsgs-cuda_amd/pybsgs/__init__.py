@@ -25,7 +25,7 @@ NATIVE_SYMBOLS = [
     "bsgs_bench_random_read", "bsgs_bench_stream", "bsgs_bench_modmul", "bsgs_set_tiles_per_launch", "bsgs_launch_count", "bsgs_build_baby_tables", "bsgs_build_baby_tables_device", "bsgs_build_baby_table_ext", "bsgs_ext_overflow_capacity", "bsgs_build_baby_table_ext_device", "bsgs_install_table_ext_device", "bsgs_profile_phases",
     "bsgs_set_walk", "bsgs_enqueue_walk", "bsgs_run_walk", "bsgs_walk_centres", "bsgs_set_flags", "bsgs_quirk_count", "bsgs_broadcast_tables",
     "bsgs_tiles_per_launch", "bsgs_engine_geometry", "bsgs_run_digest", "bsgs_selftest_lo64", "bsgs_compat_stats", "bsgs_debug_buffers", "bsgs_alloc_stats", "bsgs_tune_placement", "bsgs_chain_placement", "bsgs_chain_grades", "bsgs_debug_grade_rule", "bsgs_debug_xcd_profile",
-    "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_narrow_batching",
+    "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
@@ -149,6 +149,7 @@ def lib():
             "bsgs_tiles_per_launch": [vp, C.POINTER(C.c_uint32)],
             "bsgs_engine_geometry": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
             "bsgs_debug_last_batching": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+            "bsgs_debug_last_tiles_per_block": [vp, C.POINTER(C.c_uint32)],
             "bsgs_debug_narrow_batching": [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
             "bsgs_run_digest": [vp, u8p, C.c_uint32, vp, C.POINTER(HitEx), C.c_uint32, C.POINTER(C.c_uint32)],
             "bsgs_selftest_lo64": [vp, u8p, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)],
@@ -403,6 +404,12 @@ class Device:
         a, b = C.c_uint32(), C.c_uint32()
         _chk(self.L.bsgs_debug_last_batching(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_tiles_per_block(self):
+        """tiles per block of the most recent tile launch: 2 when the quad-chain kernel walked two tiles per block (bsgs_hip.hip launch_tiles), else 1"""
+        a = C.c_uint32()
+        _chk(self.L.bsgs_debug_last_tiles_per_block(self.h, C.byref(a)))
+        return a.value
 
     def table_info(self):
         lay, nb, ov = C.c_uint32(), C.c_uint64(), C.c_uint64()

@@ -50,79 +50,94 @@ def main():
     body = lines[a:b]
     vgpr = re.search(re.escape(KERNEL) + r"\.num_vgpr, max\((\d+)", text)
     lab = re.compile(r"^(\.LBB\d+_\d+):")
-    best = None
+    # the probe loops: the largest loop (one tile per block) and, in the quad-chain kernels of 64-byte lines, the pair walk's loop (two tiles per block: tile_pair_walk,
+    # recognised by the scalar loads of the centres inside it); both are analysed, "probe_loop_per_giant_step" stays the one-tile loop
+    loops = []
     for h, l in enumerate(body):
         m = lab.match(l)
         if not (m and "Loop Header" in l):
             continue
         back = [i for i, x in enumerate(body) if i > h and re.search(r"s_c?branch\w*\s+" + re.escape(m.group(1)) + r"$", x.strip())]
-        if back and (best is None or back[-1] - h > best[1] - best[0]):
-            best = (h, back[-1])
-    start, end = best
-    blocks, cur = [], None
-    for i in range(start, end + 1):
-        m = lab.match(body[i])
-        if m:
-            cur = {"label": m.group(1), "ins": []}
-            blocks.append(cur)
-            continue
-        t = body[i].strip()
-        if t and not t.startswith(";") and not t.startswith("."):
-            cur["ins"].append(t.split()[0])
-    # lane_moves = v_readlane_b32 / v_writelane_b32: what an SGPR the register allocator could not keep costs inside the loop (it parks scalars in lanes of a VGPR; the
-    # compiler remark "SGPRs Spill" counts the parked registers, this counts the instructions that move them, per class of block)
-    classes = collections.defaultdict(lambda: {"blocks": 0, "valu": 0, "mad64": 0, "carry": 0, "plain": 0, "lane_moves": 0, "s_nop": 0, "lds": 0, "vmem": 0})
-    rare_tail = False
-    for k, blk in enumerate(blocks):
-        c = collections.Counter(blk["ins"])
-        mads = c.get("v_mad_u64_u32", 0)
-        valu = sum(v for n, v in c.items() if n.startswith("v_"))
-        # the equal-x doubling path: a full-width squaring (49 multiply-adds) or the Px^2 squaring (45), only entered under an exec branch
-        if mads >= 60:
-            kind = "M"
-        elif 40 <= mads < 60:
-            kind = "rare"
-        elif 20 <= mads < 40:
-            kind = "S"
-        else:
-            kind = "glue"
-        # hit-report blocks: global store + atomic, reached only when a ballot is non-zero
-        if kind == "glue" and any(n.startswith("global_atomic") or n.startswith("global_store") for n in c):
-            kind = "rare"
-        # everything between the start of the equal-x path and the next block that touches memory (the prefetch / probe issue of
-        # the main path) belongs to that path: its two field additions, its multiplication, its full-width squaring
-        has_mem = any(n.startswith("ds_") or n.startswith("global_") or n.startswith("buffer_") for n in c)
-        if rare_tail and not has_mem:
-            kind = "rare"
-        else:
-            rare_tail = False
-        if 40 <= mads < 60:
-            rare_tail = True
-        blk["kind"] = kind
-        d = classes[kind]
-        d["blocks"] += 1
-        d["valu"] += valu
-        d["s_nop"] += c.get("s_nop", 0)
-        d["lane_moves"] += c.get("v_readlane_b32", 0) + c.get("v_writelane_b32", 0)
-        d["lds"] += sum(v for n, v in c.items() if n.startswith("ds_"))
-        d["vmem"] += sum(v for n, v in c.items() if n.startswith("global_") or n.startswith("buffer_"))
-        for n, v in c.items():
-            if n.startswith("v_"):
-                d[group(n)] += v
+        if back:
+            loops.append((h, back[-1]))
+    loops = [lp for lp in loops if not any(o != lp and o[0] <= lp[0] and lp[1] <= o[1] for o in loops)]      # outermost only
+    loops = [lp for lp in loops if sum(1 for x in body[lp[0]:lp[1]] if x.strip().startswith("v_mad_u64_u32")) >= 8 * 60]  # probe loops: >= 8 multiplications
+    pair = [lp for lp in loops if any("s_load_dwordx8" in x for x in body[lp[0]:lp[1]])]
+    single = [lp for lp in loops if lp not in pair]
+    largest = max(single, key=lambda lp: lp[1] - lp[0])
+
+    def analyse(start, end):
+        blocks, cur = [], None
+        for i in range(start, end + 1):
+            m = lab.match(body[i])
+            if m:
+                cur = {"label": m.group(1), "ins": []}
+                blocks.append(cur)
+                continue
+            t = body[i].strip()
+            if t and not t.startswith(";") and not t.startswith("."):
+                cur["ins"].append(t.split()[0])
+        # lane_moves = v_readlane_b32 / v_writelane_b32: what an SGPR the register allocator could not keep costs inside the loop (it parks scalars in lanes of a VGPR; the
+        # compiler remark "SGPRs Spill" counts the parked registers, this counts the instructions that move them, per class of block)
+        classes = collections.defaultdict(lambda: {"blocks": 0, "valu": 0, "mad64": 0, "carry": 0, "plain": 0, "lane_moves": 0, "s_nop": 0, "lds": 0, "vmem": 0, "smem": 0})
+        rare_tail = False
+        for k, blk in enumerate(blocks):
+            c = collections.Counter(blk["ins"])
+            mads = c.get("v_mad_u64_u32", 0)
+            valu = sum(v for n, v in c.items() if n.startswith("v_"))
+            # the equal-x doubling path: a full-width squaring (49 multiply-adds) or the Px^2 squaring (45), only entered under an exec branch
+            if mads >= 60:
+                kind = "M"
+            elif 40 <= mads < 60:
+                kind = "rare"
+            elif 20 <= mads < 40:
+                kind = "S"
+            else:
+                kind = "glue"
+            # hit-report blocks: global store + atomic, reached only when a ballot is non-zero
+            if kind == "glue" and any(n.startswith("global_atomic") or n.startswith("global_store") for n in c):
+                kind = "rare"
+            # everything between the start of the equal-x path and the next block that touches memory (the prefetch / probe issue of
+            # the main path) belongs to that path: its two field additions, its multiplication, its full-width squaring
+            has_mem = any(n.startswith("ds_") or n.startswith("global_") or n.startswith("buffer_") for n in c)
+            if rare_tail and not has_mem:
+                kind = "rare"
+            else:
+                rare_tail = False
+            if 40 <= mads < 60:
+                rare_tail = True
+            blk["kind"] = kind
+            d = classes[kind]
+            d["blocks"] += 1
+            d["valu"] += valu
+            d["s_nop"] += c.get("s_nop", 0)
+            d["lane_moves"] += c.get("v_readlane_b32", 0) + c.get("v_writelane_b32", 0)
+            d["lds"] += sum(v for n, v in c.items() if n.startswith("ds_"))
+            d["vmem"] += sum(v for n, v in c.items() if n.startswith("global_") or n.startswith("buffer_"))
+            d["smem"] += sum(v for n, v in c.items() if n.startswith("s_load_"))
+            for n, v in c.items():
+                if n.startswith("v_"):
+                    d[group(n)] += v
+        out_classes = {}
+        for kind, d in classes.items():
+            d["issue_cycles"] = round(sum(d[g] * COST[g] for g in COST), 1)
+            out_classes[kind] = d
+        main_path = [out_classes[k] for k in ("M", "S", "glue") if k in out_classes]
+        steps_per_iteration = 8.0 if KERNEL.endswith("ELb1EEv8TileArgs") else 4.0      # quad chain: one iteration = four giants (or 2 giants x 2 tiles); pair chain: two
+        per_step = {g: sum(d[g] for d in main_path) / steps_per_iteration for g in ("valu", "mad64", "carry", "plain", "lane_moves", "vmem", "smem")}
+        ps = {k: round(v, 2 if k in ("vmem", "smem") else 1) for k, v in per_step.items()}
+        ps["issue_cycles"] = round(sum(per_step[g] * COST[g] for g in COST), 1)
+        return out_classes, ps
+
     mode = re.search(r"kernelILi(\d)", KERNEL).group(1)
     whole = collections.Counter(x.strip().split()[0] for x in body if x.strip() and not x.strip().startswith((";", ".")))
     res = {"kernel": "giant_pair2_kernel<%s, false, %s>" % (mode, "true" if KERNEL.endswith("ELb1EEv8TileArgs") else "false"), "translation_unit": TU,
            "lane_moves_whole_kernel": {"v_readlane_b32": whole.get("v_readlane_b32", 0), "v_writelane_b32": whole.get("v_writelane_b32", 0)}, "vgprs": int(vgpr.group(1)) if vgpr else None,
-           "loop": "one iteration = four giants = 8 giant steps (quad chain) or one pair of giants = 4 giant steps (pair chain); two x coordinates per giant",
-           "cost_cycles_per_wave_instruction": COST, "classes": {}}
-    for kind, d in classes.items():
-        d["issue_cycles"] = round(sum(d[g] * COST[g] for g in COST), 1)
-        res["classes"][kind] = d
-    main_path = [res["classes"][k] for k in ("M", "S", "glue") if k in res["classes"]]
-    steps_per_iteration = 8.0 if KERNEL.endswith("ELb1EEv8TileArgs") else 4.0      # quad chain: one iteration = four giants; pair chain: two
-    per_step = {g: sum(d[g] for d in main_path) / steps_per_iteration for g in ("valu", "mad64", "carry", "plain", "lane_moves")}
-    res["probe_loop_per_giant_step"] = {k: round(v, 1) for k, v in per_step.items()}
-    res["probe_loop_per_giant_step"]["issue_cycles"] = round(sum(per_step[g] * COST[g] for g in COST), 1)
+           "loop": "one iteration = four giants = 8 giant steps (quad chain; the pair walk: two giants of two tiles) or one pair of giants = 4 giant steps (pair chain); two x coordinates per giant",
+           "cost_cycles_per_wave_instruction": COST}
+    res["classes"], res["probe_loop_per_giant_step"] = analyse(*largest)
+    if pair:
+        res["pair_walk_classes"], res["pair_walk_loop_per_giant_step"] = analyse(*pair[0])
     m = res["classes"].get("M")
     if m:
         res["one_multiplication"] = {g: round(m[g] / m["blocks"], 1) for g in ("valu", "mad64", "carry", "plain")}
