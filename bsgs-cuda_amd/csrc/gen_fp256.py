@@ -190,28 +190,30 @@ def gen_sqr():
     return "".join(out)
 
 
-def gen_sqr_lo10():
-    """words 0..9 of a*a, exactly: the cross products of columns 1..9 (22 of the 28), doubled, plus the diagonal squares a0^2..a4^2.
-    What the low-64-bit x coordinate needs of lambda^2 (fp256.hip.h: fe_sqr_add2_lo64): words 0, 1, 7, 8, 9 and the carries through
-    the words in between."""
+def gen_sqr_win69():
+    """words 7..9 of the band of a*a made of columns 6..9 only: the 13 cross products of those columns, doubled, plus a3^2 and a4^2
+    (15 of the 36 products).  What the low-64-bit x coordinate needs of lambda^2 besides words 0 and 1 (fp256.hip.h: fe_sqr_add2_lo64,
+    which bounds the carry of the dropped columns 2..5 into word 7).  Column 6 starts from zero; the carries of columns 8 and 9 only
+    reach words 10 and 11, so those two columns count none (their sums wrap mod 2^64 without changing words 8 and 9)."""
     out = []
-    out.append("__device__ __forceinline__ void fe_sqr_lo10(u32 (&r)[10], const u32 (&a)[8])\n{\n")
-    out.append("    u64 acc = 0; u32 c2; u64 cyA, cyB, cyC; u32 x[10];\n    x[0] = 0;\n")
-    for k in range(1, 10):
+    out.append("__device__ __forceinline__ void fe_sqr_win69(u32 (&r)[3], const u32 (&a)[8])\n{\n")
+    out.append("    u64 acc = 0; u32 c2; u64 cyA, cyB, cyC; u32 x[10];\n")
+    for k in range(6, 10):
         prods = [(i, k - i) for i in range(8) if 0 <= k - i <= 7 and i < k - i]
-        out.append(column_asm(prods, "a", "a", k == 1, can_carry=k not in (1, 2)))
+        out.append(column_asm(prods, "a", "a", k == 6, can_carry=k in (6, 7)))
         if k < 9:
             out.append("    x[%d] = (u32)acc; acc = (acc >> 32) | ((u64)c2 << 32);\n" % k)
         else:
             out.append("    x[%d] = (u32)acc;\n" % k)
     out.append("    u64 d[5];\n")
-    for i in range(5):
+    for i in (3, 4):
         out.append('    asm("v_mad_u64_u32 %%0, vcc, %%1, %%1, 0" : "=v"(d[%d]) : "v"(a[%d]) : "vcc");\n' % (i, i))
-    out.append("    u32 c = 0, co;\n")
-    for k in range(10):
-        dbl = "(x[0] << 1)" if k == 0 else "__builtin_amdgcn_alignbit(x[%d], x[%d], 31)" % (k, k - 1)
+    # word 6 of the band is needed only for its carry into word 7
+    out.append("    u32 c, co;\n")
+    out.append("    (void)__builtin_addc((x[6] << 1), (u32)d[3], 0u, &c);\n")
+    for k in range(7, 10):
         dw = "(u32)d[%d]" % (k // 2) if k % 2 == 0 else "(u32)(d[%d] >> 32)" % (k // 2)
-        out.append("    r[%d] = __builtin_addc(%s, %s, c, &co); c = co;\n" % (k, dbl, dw))
+        out.append("    r[%d] = __builtin_addc(__builtin_amdgcn_alignbit(x[%d], x[%d], 31), %s, c, &co); c = co;\n" % (k - 7, k, k - 1, dw))
     out.append("}\n\n")
     return "".join(out)
 
@@ -220,4 +222,4 @@ if __name__ == "__main__":
     sys.stdout.write(gen_mul())
     sys.stdout.write(gen_mul_salu())
     sys.stdout.write(gen_sqr())
-    sys.stdout.write(gen_sqr_lo10())
+    sys.stdout.write(gen_sqr_win69())
