@@ -3,7 +3,7 @@
 # run, next to the launch time of that run: do the run-to-run levels show in a clock other than sclk?
 R=${GRAFT_REPO_ROOT:-.}
 for i in $(seq 1 ${1:-4}); do
-  python $R/bench.py --no-cpu-baseline --steps 40 --warmup 3 2>/dev/null > /tmp/clk_bench.json &
+  python $R/bench.py --full --no-cpu-baseline --steps 40 --warmup 3 2>/dev/null > /tmp/clk_bench.json &
   BP=$!
   while kill -0 $BP 2>/dev/null; do
     rocm-smi -c --showpower --json 2>/dev/null | python -c "
