@@ -181,6 +181,7 @@ extern "C" int bsgs_dev_close(bsgs_dev *d)
     (void)hipStreamSynchronize(d->stream);
     release_pending(d);
     free_table(d); free_g2(d); bsgs_free_recv(d);
+    bsgs_kangaroo_release(d);
     release_grader(d);
     free_reserve(d);
     park_release(d->id);

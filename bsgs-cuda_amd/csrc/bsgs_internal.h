@@ -14,6 +14,8 @@ int bsgs_fail(int code, const char *fmt, ...);
     } while (0)
 #define fail bsgs_fail
 
+struct bsgs_kangaroo;                      // kangaroo.hip: the herd, its scratch, jump table and record buffer
+
 struct bsgs_dev {
     int id = 0;
     hipStream_t stream = nullptr;          // the engine's one stream: uploads, relayouts, tile launches, read-backs
@@ -97,6 +99,7 @@ struct bsgs_dev {
     // (bsgs_lines_malloc: tables above 40 GiB get a memory group reserved for the chain scratch), owned by the engine
     void *recv_lines = nullptr, *recv_ovf = nullptr;
     const char *last_kernel = "";          // the tile kernel instantiation of the most recent launch (bsgs_debug_last_kernel)
+    bsgs_kangaroo *kangaroo = nullptr;     // bsgs_kangaroo_setup: independent of giants and table
 };
 
 // the big, long-lived device buffers (bucket lines, chain scratch, giants).  BSGS_CONTIGUOUS=1: ask for physically contiguous
@@ -131,6 +134,7 @@ static inline size_t bsgs_hitbuf_bytes(const bsgs_dev *d) { return 64 + (size_t)
 static inline void bsgs_le_to_fe(fe &f, const uint8_t *le) { memcpy(f.v, le, 32); }
 uint64_t bsgs_ovf_slots(uint64_t entries);                   // size of the overflow hash set for `entries` keys (power of two, load <= 1/2)
 int bsgs_ovf_fill(bsgs_dev *d, const u64 *list, uint64_t n, u64 *table, uint64_t slots);   // table := hash set of list[0..n)
+void bsgs_kangaroo_release(bsgs_dev *d);                     // kangaroo.hip: frees the herd (bsgs_dev_close, a new bsgs_kangaroo_setup)
 // hand a finished "lines + overflow list" table to the engine (it becomes the owner of both buffers)
 int bsgs_install_lines(bsgs_dev *d, u32x4 *lines, int lplog, u64 *ovf, uint64_t ovf_n, uint64_t ht_items, uint64_t w,
                        uint64_t overflow_buckets);

@@ -270,11 +270,9 @@ void search_job(const Run &R, JobList &jobs, const LaneEngines &E, const JobList
     const double secs = since(t0);
     std::string win;
     if (J.found) {                                                    // win.txt 1_9_7File.pb:5146-5160
-        const std::string head = "KEY[" + std::to_string(J.listpos) + "]: ";
-        const std::string l1 = head + "0x" + hs::fe_to_hex(J.winkey);
-        const std::string l2 = std::string(head.size() - 5, ' ') + "Pub: " + hs::compress_pubkey(realpub);
-        o.say("\n****************************\n%s\n%s\n****************************\n", l1.c_str(), l2.c_str());
-        win = l1 + "\r\n" + l2 + "\r\n";
+        std::string console;
+        win = key_lines(J.listpos, J.winkey, realpub, console);
+        o.say("%s", console.c_str());
     } else o.say("\nReached end of space\n");
     o.say("Job time %.2fs, %llu tiles, %.3e giant steps\n", secs, (unsigned long long)J.tiles_done.load(), (double)J.steps_done.load());
     o.say("Checker: %llu hits resolved in %.3fs of CPU time (%.2f%% of one core)\n", (unsigned long long)J.hits_checked.load(), J.checker_ns.load() * 1e-9,
@@ -286,6 +284,7 @@ void search_job(const Run &R, JobList &jobs, const LaneEngines &E, const JobList
 int main(int argc, char **argv)
 {
     if (argc >= 2 && std::string(argv[1]) == "-selftest") return selftest(argc, argv);
+    for (int i = 1; i < argc; i++) if (strcasecmp(argv[i], "-kangaroo") == 0) return kangaroo_main(argc, argv);     // host_kangaroo.cpp
     printf("BSGS MI355X (drop-in for bsgscudaHT 1.9.7-file0) on %s\n", bsgs_version());
     Run R;
     R.cfg = parse_args(argc, argv);

@@ -222,3 +222,8 @@ void test_corrupt_engine(const std::vector<bsgs_dev *> &devs);       // test bui
 void per_gpu(const std::vector<int> &gpus, const std::function<void(size_t)> &fn);
 void gpu_thread(Job *J, int gpu, int slot, bsgs_dev *dev);
 int selftest(int argc, char **argv);
+// the lines a found key is reported with (1_9_7File.pb:5146-5160): returns the win.txt text, `console` receives the console block
+std::string key_lines(int listpos, const Scalar &key, const Affine &pub, std::string &console);
+// host_kangaroo.cpp: bsgs_mi355x -kangaroo, and -selftest kangaroo (the table of distinguished points on a scripted record stream)
+int kangaroo_main(int argc, char **argv);
+int kangaroo_selftest(const std::vector<std::string> &args);

@@ -13,6 +13,15 @@ void derive_constants(Run &R)
     R.pubadd = hs::affine_neg(hs::point_mul(hs::G, R.gstep));
 }
 std::string pub_hex(const Affine &q) { return hs::fe_to_hex(q.x) + hs::fe_to_hex(q.y); }
+// win.txt 1_9_7File.pb:5146-5160
+std::string key_lines(int listpos, const Scalar &key, const Affine &pub, std::string &console)
+{
+    const std::string head = "KEY[" + std::to_string(listpos) + "]: ";
+    const std::string l1 = head + "0x" + hs::fe_to_hex(key);
+    const std::string l2 = std::string(head.size() - 5, ' ') + "Pub: " + hs::compress_pubkey(pub);
+    console = "\n****************************\n" + l1 + "\n" + l2 + "\n****************************\n";
+    return l1 + "\r\n" + l2 + "\r\n";
+}
 // dispenser seed (1_9_7File.pb:5046-5064)
 Job::Job(const Run &run, int listpos, const Affine &realpub, const Affine &findpub, const Scalar &key0, size_t engines, FILE *joblog)
     : run(run), listpos(listpos), realpub(realpub), findpub(findpub), pub_hex(::pub_hex(realpub)), joblog(joblog),

@@ -135,6 +135,8 @@ int selftest(int argc, char **argv)
                 J.inflight.push_back(v); J.inflight_valid.push_back(valid);
             }
             save_checkpoint(R.cfg, J.listpos, "selftest", J.checkpoint_counter());
+        } else if (a[i] == "kangaroo") {                                    // the rest of the command line: range, public key, record stream (host_kangaroo.cpp)
+            return kangaroo_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "joblist" && i + 1 < a.size()) {                  // the rest of the command line is the script
             return selftest_joblist(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else { fprintf(stderr, "selftest: unknown item %s\n", a[i].c_str()); return 2; }

@@ -27,6 +27,7 @@ NATIVE_SYMBOLS = [
     "bsgs_tiles_per_launch", "bsgs_engine_geometry", "bsgs_run_digest", "bsgs_selftest_lo64", "bsgs_compat_stats", "bsgs_debug_buffers", "bsgs_alloc_stats", "bsgs_tune_placement", "bsgs_chain_placement", "bsgs_chain_grades", "bsgs_debug_grade_rule", "bsgs_debug_xcd_profile",
     "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
+    "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc"]
@@ -55,6 +56,16 @@ class Hit(C.Structure):
 class HitEx(C.Structure):
     _fields_ = [("code", C.c_uint32), ("idx", C.c_uint32), ("tile", C.c_uint32), ("reserved", C.c_uint32)]
 
+
+class KangarooState(C.Structure):
+    _fields_ = [("x", C.c_uint8 * 32), ("y", C.c_uint8 * 32), ("d", C.c_uint8 * 16), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class KangarooRecord(C.Structure):
+    _fields_ = [("x", C.c_uint8 * 32), ("d", C.c_uint8 * 16), ("kangaroo", C.c_uint32), ("flags", C.c_uint32), ("step", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+KANGAROO_JUMPS, KANGAROO_WILD, KANGAROO_DEAD = 64, 1, 0x80000000
 
 _lib = None
 
@@ -156,6 +167,12 @@ def lib():
             "bsgs_debug_buffers": [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
             "bsgs_debug_realloc": [vp, C.c_int, C.c_uint64],
             "bsgs_debug_xcd_profile": [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
+            "bsgs_kangaroo_setup": [vp, u8p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
+            "bsgs_kangaroo_upload": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
+            "bsgs_kangaroo_upload_list": [vp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(KangarooState)],
+            "bsgs_kangaroo_download": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
+            "bsgs_kangaroo_run": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
+            "bsgs_kangaroo_geometry": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         }
         for name, args in sig.items():
             fn = getattr(L, name, None)
@@ -593,3 +610,49 @@ class Device:
         g = C.c_double()
         _chk(self.L.bsgs_bench_modmul(self.h, C.byref(g)))
         return g.value
+
+    # ---- kangaroo walk (include/bsgs_hip.h "Kangaroo"): states are (x, y, d, flags) with d an integer mod 2^128 (two's complement), records dicts
+    def kangaroo_setup(self, jumps, scalars, dp, herd, per_thread, record_cap):
+        """jumps = 64 affine points (x, y), scalars = their s_j; herd kangaroos, per_thread of them per GPU thread; record_cap records per launch"""
+        if len(jumps) != KANGAROO_JUMPS or len(scalars) != KANGAROO_JUMPS:
+            raise BsgsError("kangaroo_setup: %d jump points and scalars" % KANGAROO_JUMPS)
+        xy = b"".join(le32(x) + le32(y) for x, y in jumps)
+        _chk(self.L.bsgs_kangaroo_setup(self.h, xy, (C.c_uint64 * KANGAROO_JUMPS)(*scalars), dp, herd, per_thread, record_cap))
+        self._kang_cap = record_cap
+
+    @staticmethod
+    def _kangaroo_states(states):
+        arr = (KangarooState * len(states))()
+        for k, (x, y, d, fl) in enumerate(states):
+            arr[k].x[:] = le32(x)
+            arr[k].y[:] = le32(y)
+            arr[k].d[:] = (d % (1 << 128)).to_bytes(16, "little")
+            arr[k].flags = fl
+        return arr
+
+    def kangaroo_upload(self, first, states):
+        _chk(self.L.bsgs_kangaroo_upload(self.h, first, len(states), self._kangaroo_states(states)))
+
+    def kangaroo_upload_list(self, idx, states):
+        assert len(idx) == len(states)
+        _chk(self.L.bsgs_kangaroo_upload_list(self.h, (C.c_uint32 * len(idx))(*idx), len(idx), self._kangaroo_states(states)))
+
+    def kangaroo_download(self, first, n):
+        arr = (KangarooState * n)()
+        _chk(self.L.bsgs_kangaroo_download(self.h, first, n, arr))
+        return [(int.from_bytes(bytes(s.x), "little"), int.from_bytes(bytes(s.y), "little"), int.from_bytes(bytes(s.d), "little"), s.flags) for s in arr]
+
+    def kangaroo_run(self, steps):
+        """one launch of `steps` steps: (records, dropped, kernel ms); a record is {x, d (mod 2^128), kangaroo, flags, step}"""
+        cap = self._kang_cap
+        recs = (KangarooRecord * cap)()
+        n, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_float()
+        _chk(self.L.bsgs_kangaroo_run(self.h, steps, recs, cap, C.byref(n), C.byref(dropped), C.byref(ms)))
+        out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step}
+               for r in recs[:n.value]]
+        return out, dropped.value, ms.value
+
+    def kangaroo_geometry(self):
+        t, g, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _chk(self.L.bsgs_kangaroo_geometry(self.h, C.byref(t), C.byref(g), C.byref(b)))
+        return t.value, g.value, b.value

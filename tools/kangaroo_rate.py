@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
+launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
+
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--out FILE]
+
+The starts are 65536 distinct points P0 + i*G, repeated over the herd (the walk's cost does not depend on which point a kangaroo stands on; repeats only
+make their DPs coincide)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "bsgs-cuda_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import pybsgs                                     # noqa: E402
+from pybsgs.ecpy import G, add, mul               # noqa: E402
+
+# bytes of HBM traffic per kangaroo step (csrc/kangaroo.hip): pass 1 reads x (32) and flags (4) and writes the running product (32); pass 2 reads x, flags, the
+# previous running product, y and d (32 + 4 + 32 + 32 + 16) and writes x, y, d (80).  DP records (64 bytes each, 2^-dp of the steps) come on top.
+BYTES_PER_STEP = 32 + 4 + 32 + (32 + 4 + 32 + 32 + 16) + 80
+
+
+def vgprs():
+    try:
+        import spill_report
+        for r in spill_report.report(tus=["kangaroo"]):
+            if "kangaroo_kernel<true>" in r["kernel"]:
+                return r["vgprs"]
+    except (SystemExit, Exception):
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--launches", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dp", type=int, default=16)
+    ap.add_argument("--per-thread", type=int, default=16)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    dev = pybsgs.Device(0)
+    L = dev.L
+    cus = C.c_int()
+    pybsgs._chk(L.bsgs_dev_cu_count(dev.h, C.byref(cus)))
+    n = cus.value * 1024 * a.per_thread
+    scal = [(0x9E3779B97F4A7C15 * (j + 1)) % (1 << 62) + 1 for j in range(64)]
+    dev.kangaroo_setup([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
+    distinct = 65536
+    p = mul(0xC0FFEE << 60)
+    one = []
+    for i in range(distinct):
+        one.append(p[0].to_bytes(32, "little") + p[1].to_bytes(32, "little") + (i & 0xFFFFFFFF).to_bytes(16, "little") + (i & 1).to_bytes(4, "little") + bytes(12))
+        p = add(p, G)
+    blob = b"".join(one) * (n // distinct)
+    arr = (pybsgs.KangarooState * n).from_buffer_copy(blob)
+    pybsgs._chk(L.bsgs_kangaroo_upload(dev.h, 0, n, arr))
+    recs = (pybsgs.KangarooRecord * (1 << 22))()
+    cnt, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_float()
+
+    def launch():
+        pybsgs._chk(L.bsgs_kangaroo_run(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(dropped), C.byref(ms)))
+        return ms.value, cnt.value + dropped.value
+
+    for _ in range(a.warmup):
+        launch()
+    kms, nrec = [], 0
+    t0 = time.perf_counter()
+    for _ in range(a.launches):
+        k, r = launch()
+        kms.append(k)
+        nrec += r
+    wall = time.perf_counter() - t0
+    steps = n * a.steps * a.launches
+    res = {"what": "kangaroo walk rate, one engine, full herd", "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp,
+           "launches": a.launches, "steps_per_s": steps / wall, "steps_per_s_kernel": steps / (sum(kms) / 1e3), "ms_per_launch": sum(kms) / len(kms),
+           "ms_per_launch_min": min(kms), "bytes_per_step": BYTES_PER_STEP, "hbm_GBps_implied": steps * BYTES_PER_STEP / (sum(kms) / 1e3) / 1e9,
+           "records_per_launch": nrec / a.launches, "vgprs": vgprs()}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    dev.close()
+
+
+if __name__ == "__main__":
+    main()
