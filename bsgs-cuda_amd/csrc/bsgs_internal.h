@@ -14,7 +14,18 @@ int bsgs_fail(int code, const char *fmt, ...);
     } while (0)
 #define fail bsgs_fail
 
-struct bsgs_kangaroo;                      // kangaroo.hip: the herd, its scratch, jump table and record buffer
+// kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table and the staging of bsgs_kangaroo_seed
+struct bsgs_kangaroo {
+    u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
+    u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
+    uint8_t *rec_host = nullptr;
+    uint32_t N = 0, G = 0, T = 0, block = 0, dp = 0, cap = 0, staging_n = 0;
+    u32x4 *comb = nullptr;                 // 16 x 255 affine points v * 2^(8k) * G, x || y (64 bytes each): built at the first seed call
+    u32x4 *seed_in = nullptr;              // one chunk of a seed call: offsets [cap] | flags [cap] | index list [cap]
+    u32x4 *seed_z = nullptr;               // the chunk's Jacobian Z, [2][cap]
+    u32 *seed_out = nullptr;               // {kangaroos at infinity, lowest position of one}
+    uint32_t seed_cap = 0;
+};
 
 struct bsgs_dev {
     int id = 0;

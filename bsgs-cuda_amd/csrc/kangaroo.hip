@@ -179,18 +179,12 @@ __global__ void kangaroo_gather_kernel(const u32x4 *st, const u32 *flags, u32 N,
 }
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
-struct bsgs_kangaroo {
-    u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
-    u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
-    uint8_t *rec_host = nullptr;
-    uint32_t N = 0, G = 0, T = 0, block = 0, dp = 0, cap = 0, staging_n = 0;
-};
-
 void bsgs_kangaroo_release(bsgs_dev *d)
 {
     bsgs_kangaroo *k = d->kangaroo;
     if (!k) return;
-    for (void *p : {(void *)k->st, (void *)k->chain, (void *)k->table, (void *)k->staging, (void *)k->flags, (void *)k->rec, (void *)k->idx})
+    for (void *p : {(void *)k->st, (void *)k->chain, (void *)k->table, (void *)k->staging, (void *)k->flags, (void *)k->rec, (void *)k->idx, (void *)k->comb,
+                    (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out})
         if (p) (void)hipFree(p);
     if (k->rec_host) (void)hipHostFree(k->rec_host);
     delete k;

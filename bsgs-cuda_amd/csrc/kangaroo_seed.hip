@@ -1,0 +1,281 @@
+// kangaroo_seed.hip -- the start points of kangaroos on gfx950: offsets d in, states (d*G or Q + d*G, d, flags) out (include/bsgs_hip.h, "Kangaroo":
+// bsgs_kangaroo_seed).  What the host's comb did on CPU threads before every run and between launches at every re-seed.
+//
+// Fixed-base comb, 16 windows of 8 bits: table T[k][v] = v * 2^(8k) * G for v = 1..255 (4080 affine points, 255 KiB, built once per herd on the host and
+// kept in device memory; it stays in L2).  A thread takes B positions of the call, k = b * TT + thread (a wave's staging and state accesses are contiguous).
+// Pass 1, per position: |d| * G by at most sixteen Jacobian mixed additions, y negated for d < 0, then + Q for a wild one; X, Y go to the kangaroo's own
+// state slots, Z to a scratch, the running product of the thread's Z's to the walk's batch scratch.  One inversion per block of four waves (fe_inv_block,
+// as the walk).  Pass 2, backwards: 1 / Z from the running products, x = X / Z^2, y = Y / Z^3 canonical, d and flags stored.
+// Inside the comb no addition is degenerate: before window k the partial sum is a multiple of G below 2^(8k), the addend a multiple of 2^(8k) below 2^128,
+// and 2^128 is far below the group order; a zero digit is skipped and the first nonzero digit is a copy.  Only + Q can double (d*G == Q) or cancel
+// (d*G == -Q): jac_madd<true> tests for both.  A start at infinity (that, or tame d = 0) puts 1 into the batch, never 0, and leaves the kangaroo dead.
+#include "bsgs_internal.h"
+#include "host_secp.h"
+
+#include <algorithm>
+
+#define SEED_REGION 6144u                                   // LDS bytes per wave for fe_inv_block<REGION, 4>
+#define SEED_LDS (4u * SEED_REGION)
+#define SEED_WINDOWS 16u
+#define SEED_CHUNK (1u << 20)                               // positions per launch: bounds the staging (52 bytes per position)
+
+struct SeedArgs {
+    u32x4 *st;             // [5][N]: x.lo, x.hi, y.lo, y.hi, d
+    u32 *flags;            // [N]
+    u32x4 *prefix;         // the walk's batch scratch (2 N vectors), here [2][N] by position: running products of Z
+    u32x4 *z;              // [2][cap] by position
+    const u32x4 *comb;     // [16][255] points, x || y
+    const u32x4 *d;        // [n] offsets, two's complement
+    const u32 *fl;         // [n] BSGS_KANGAROO_WILD or 0
+    const u32 *idx;        // [n] kangaroo of each position, or NULL: first + position
+    u32 *out;              // {count of starts at infinity, lowest position of one}
+    fe qx, qy;
+    u32 N, cap, first, n, B, TT, pos0;
+};
+
+__device__ __forceinline__ bool seed_is_zero(const fe &a)
+{
+    return (a.v[0] | a.v[1] | a.v[2] | a.v[3] | a.v[4] | a.v[5] | a.v[6] | a.v[7]) == 0u;
+}
+__device__ __forceinline__ void seed_twice(fe &r, const fe &a) { fe_add(r, a, a); fe_canon(r); }      // a canonical
+
+// (X, Y, Z) += (ax, ay): Jacobian + affine, X and Y canonical on entry and on return.  CHECK: returns 1 when the two points are equal and 2 when they are
+// opposite, (X, Y, Z) untouched; without CHECK the caller knows they are neither.  8 multiplications, 3 squarings.
+template <bool CHECK>
+__device__ __forceinline__ u32 jac_madd(fe &X, fe &Y, fe &Z, const fe &ax, const fe &ay)
+{
+    fe zz, h, r, hh, hhh, v, t;
+    fe_sqr(zz, Z);
+    fe_mul(h, ax, zz);
+    fe_sub(h, h, X);                                       // H = ax Z^2 - X
+    fe_mul(t, Z, zz);
+    fe_mul(r, ay, t);
+    fe_sub(r, r, Y);                                       // R = ay Z^3 - Y
+    if (CHECK) {
+        fe_canon(h);
+        if (__builtin_expect(seed_is_zero(h), 0)) { fe_canon(r); return seed_is_zero(r) ? 1u : 2u; }
+    }
+    fe_sqr(hh, h);
+    fe_mul(hhh, h, hh);
+    fe_canon(hhh);
+    fe_mul(v, X, hh);
+    fe_canon(v);
+    fe_mul(Z, Z, h);
+    fe_sqr(t, r);
+    fe_sub(t, t, hhh);
+    fe_sub(t, t, v);
+    fe_sub(X, t, v);                                       // X3 = R^2 - H^3 - 2 V
+    fe_canon(X);
+    fe_sub(t, v, X);
+    fe_mul(t, r, t);
+    fe_mul(hhh, Y, hhh);
+    fe_canon(hhh);
+    fe_sub(Y, t, hhh);                                     // Y3 = R (V - X3) - Y H^3
+    fe_canon(Y);
+    return 0u;
+}
+// (X, Y, Z) = 2 (ax, ay): S = 4 x y^2, M = 3 x^2, X3 = M^2 - 2 S, Y3 = M (S - X3) - 8 y^4, Z3 = 2 y
+__device__ __forceinline__ void jac_double_affine(fe &X, fe &Y, fe &Z, const fe &ax, const fe &ay)
+{
+    fe yy, s, m, t, y4;
+    fe_sqr(yy, ay);
+    fe_canon(yy);
+    fe_mul(s, ax, yy);
+    fe_canon(s);
+    seed_twice(s, s);
+    seed_twice(s, s);
+    fe_sqr(t, ax);
+    fe_canon(t);
+    seed_twice(m, t);
+    fe_add(m, m, t);
+    fe_canon(m);
+    fe_sqr(y4, yy);
+    fe_canon(y4);
+    seed_twice(y4, y4);
+    seed_twice(y4, y4);
+    seed_twice(y4, y4);
+    fe_sqr(X, m);
+    fe_sub(X, X, s);
+    fe_sub(X, X, s);
+    fe_canon(X);
+    fe_sub(t, s, X);
+    fe_mul(t, m, t);
+    fe_sub(Y, t, y4);
+    fe_canon(Y);
+    seed_twice(Z, ay);
+}
+
+__global__ void __launch_bounds__(256) kangaroo_seed_kernel(const SeedArgs A)
+{
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;            // the launch has exactly TT threads, B * TT >= n
+    const u32 lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 N = A.N, n = A.n, TT = A.TT;
+    u32x4 *const sx0 = A.st, *const sx1 = A.st + N, *const sy0 = A.st + 2 * (u64)N, *const sy1 = A.st + 3 * (u64)N, *const sd = A.st + 4 * (u64)N;
+    fe acc;
+    fe_set_one(acc);
+    u32 infinite = 0;                                                // bit b: position b * TT + t starts at infinity
+#pragma nounroll
+    for (u32 b = 0; b < A.B; b++) {
+        const u32 k = b * TT + t;
+        if (k >= n) break;                                           // (positions only grow with b)
+        const u32 i = A.idx ? A.idx[k] : A.first + k;
+        const u32x4 dv = A.d[k];
+        const bool wild = (A.fl[k] & BSGS_KANGAROO_WILD) != 0u, neg = (dv.w >> 31) != 0u;
+        u32 m0 = dv.x, m1 = dv.y, m2 = dv.z, m3 = dv.w;              // |d|
+        if (neg) {
+            u32 c = 0, co;
+            m0 = __builtin_subc(0u, m0, c, &co); c = co;
+            m1 = __builtin_subc(0u, m1, c, &co); c = co;
+            m2 = __builtin_subc(0u, m2, c, &co); c = co;
+            m3 = __builtin_subc(0u, m3, c, &co);
+        }
+        fe X, Y, Z;
+        bool empty = true;
+#pragma nounroll
+        for (u32 w = 0; w < SEED_WINDOWS; w++) {
+            const u32 v = m0 & 255u;
+            m0 = (m0 >> 8) | (m1 << 24); m1 = (m1 >> 8) | (m2 << 24); m2 = (m2 >> 8) | (m3 << 24); m3 >>= 8;
+            if (!v) continue;
+            const u32x4 *p = A.comb + (u64)(w * 255u + v - 1u) * 4u;
+            fe ax, ay;
+            fe_load2(ax, p, p + 1);
+            fe_load2(ay, p + 2, p + 3);
+            if (empty) { X = ax; Y = ay; fe_set_one(Z); empty = false; }
+            else jac_madd<false>(X, Y, Z, ax, ay);
+        }
+        if (neg && !empty) fe_neg(Y, Y);                             // (no point of the curve has y = 0)
+        if (wild) {
+            if (empty) { X = A.qx; Y = A.qy; fe_set_one(Z); empty = false; }
+            else {
+                const u32 kind = jac_madd<true>(X, Y, Z, A.qx, A.qy);
+                if (__builtin_expect(kind == 1u, 0)) jac_double_affine(X, Y, Z, A.qx, A.qy);
+                else if (__builtin_expect(kind == 2u, 0)) empty = true;
+            }
+        }
+        if (empty) { fe_set_one(Z); infinite |= 1u << b; }
+        else if (i < N) { fe_store2(sx0 + i, sx1 + i, X); fe_store2(sy0 + i, sy1 + i, Y); }
+        fe_mul(acc, acc, Z);
+        fe_store2(A.z + k, A.z + A.cap + k, Z);
+        fe_store2(A.prefix + k, A.prefix + N + k, acc);
+    }
+    fe inv;
+    fe_inv_block<SEED_REGION, 4>(inv, acc, lane, wave, blockIdx.x & 3u);
+#pragma nounroll
+    for (u32 bb = 0; bb < A.B; bb++) {
+        const u32 b = A.B - 1u - bb;
+        const u32 k = b * TT + t;
+        if (k >= n) continue;
+        fe zi;
+        if (b > 0) {
+            fe c, z;
+            fe_load2(c, A.prefix + (k - TT), A.prefix + N + (k - TT));
+            fe_load2(z, A.z + k, A.z + A.cap + k);
+            fe_mul(zi, inv, c);
+            fe_mul(inv, inv, z);
+        } else zi = inv;
+        const u32 i = A.idx ? A.idx[k] : A.first + k;
+        if (i >= N) continue;                                        // (the host has checked: never taken)
+        const u32 fl = A.fl[k] & BSGS_KANGAROO_WILD;
+        sd[i] = A.d[k];
+        if (__builtin_expect((infinite >> b) & 1u, 0)) {
+            const u32x4 zero = {0u, 0u, 0u, 0u};
+            sx0[i] = zero; sx1[i] = zero; sy0[i] = zero; sy1[i] = zero;
+            A.flags[i] = fl | BSGS_KANGAROO_DEAD;
+            atomicAdd(A.out, 1u);
+            atomicMin(A.out + 1, A.pos0 + k);
+            continue;
+        }
+        fe X, Y, z2, z3;
+        fe_load2(X, sx0 + i, sx1 + i);
+        fe_load2(Y, sy0 + i, sy1 + i);
+        fe_sqr(z2, zi);
+        fe_mul(z3, z2, zi);
+        fe_mul(X, X, z2);
+        fe_canon(X);
+        fe_mul(Y, Y, z3);
+        fe_canon(Y);
+        fe_store2(sx0 + i, sx1 + i, X);
+        fe_store2(sy0 + i, sy1 + i, Y);
+        A.flags[i] = fl;
+    }
+}
+
+// ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
+static int seed_comb(bsgs_dev *d, bsgs_kangaroo *k)
+{
+    if (k->comb) return BSGS_OK;
+    std::vector<uint8_t> tab((size_t)SEED_WINDOWS * 255 * 64);
+    hs::Affine base = hs::G;
+    for (uint32_t w = 0; w < SEED_WINDOWS; w++) {
+        const std::vector<hs::Affine> m = hs::multiples(base, 256);          // base, 2 base, ..., 256 base
+        for (uint32_t v = 0; v < 255; v++) hs::affine_to_le(m[v], &tab[((size_t)w * 255 + v) * 64], &tab[((size_t)w * 255 + v) * 64 + 32]);
+        base = m.back();
+    }
+    HIPCHK(hipMalloc(&k->comb, tab.size()));
+    HIPCHK(hipMemcpyAsync(k->comb, tab.data(), tab.size(), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));                                 // (tab leaves scope)
+    return BSGS_OK;
+}
+
+extern "C" int bsgs_kangaroo_seed(bsgs_dev *d, const uint8_t *q_xy_le, const uint32_t *idx, uint32_t first, uint32_t n, const uint8_t *d_le,
+                                  const uint32_t *flags, uint32_t *n_infinite, uint32_t *first_infinite)
+{
+    if (!d || !d_le || !flags) return fail(BSGS_ERR_ARG, "null");
+    bsgs_kangaroo *k = d->kangaroo;
+    if (!k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
+    if (n_infinite) *n_infinite = 0;
+    if (first_infinite) *first_infinite = 0;
+    if (!n) return BSGS_OK;
+    if (n > k->N) return fail(BSGS_ERR_ARG, "%u kangaroos of %u", n, k->N);
+    if (idx) {
+        std::vector<uint32_t> s(idx, idx + n);
+        std::sort(s.begin(), s.end());
+        if (s.back() >= k->N) return fail(BSGS_ERR_ARG, "kangaroo %u of %u", s.back(), k->N);
+        if (std::adjacent_find(s.begin(), s.end()) != s.end()) return fail(BSGS_ERR_ARG, "a kangaroo is listed twice");
+    } else if ((uint64_t)first + n > k->N) return fail(BSGS_ERR_ARG, "kangaroos [%u, %u) of %u", first, first + n, k->N);
+    bool any_wild = false;
+    for (uint32_t q = 0; q < n; q++) {
+        if (flags[q] & ~BSGS_KANGAROO_WILD) return fail(BSGS_ERR_ARG, "flags of position %u: BSGS_KANGAROO_WILD or 0", q);
+        any_wild |= flags[q] != 0;
+    }
+    if (any_wild && !q_xy_le) return fail(BSGS_ERR_ARG, "wild kangaroos need Q");
+    HIPCHK(hipSetDevice(d->id));
+    if (int rc = seed_comb(d, k)) return rc;
+    const uint32_t cap = std::min(n, SEED_CHUNK);
+    if (k->seed_cap < cap) {
+        if (k->seed_in) (void)hipFree(k->seed_in);
+        if (k->seed_z) (void)hipFree(k->seed_z);
+        k->seed_in = k->seed_z = nullptr; k->seed_cap = 0;
+        HIPCHK(hipMalloc(&k->seed_in, (size_t)cap * 24));
+        HIPCHK(hipMalloc(&k->seed_z, (size_t)cap * 32));
+        k->seed_cap = cap;
+    }
+    if (!k->seed_out) HIPCHK(hipMalloc(&k->seed_out, 8));
+    static const uint32_t init[2] = {0u, 0xFFFFFFFFu};
+    HIPCHK(hipMemcpyAsync(k->seed_out, init, 8, hipMemcpyHostToDevice, d->stream));
+    SeedArgs A;
+    memset(&A, 0, sizeof A);
+    A.st = k->st; A.flags = k->flags; A.prefix = k->chain; A.z = k->seed_z; A.comb = k->comb; A.out = k->seed_out;
+    A.d = k->seed_in;
+    A.fl = (const u32 *)(k->seed_in + k->seed_cap);
+    A.idx = idx ? A.fl + k->seed_cap : nullptr;
+    if (q_xy_le) { memcpy(A.qx.v, q_xy_le, 32); memcpy(A.qy.v, q_xy_le + 32, 32); }
+    A.N = k->N; A.cap = k->seed_cap;
+    for (uint32_t pos = 0; pos < n; pos += SEED_CHUNK) {
+        const uint32_t m = std::min(n - pos, SEED_CHUNK);
+        HIPCHK(hipMemcpyAsync((void *)A.d, d_le + (size_t)pos * 16, (size_t)m * 16, hipMemcpyHostToDevice, d->stream));
+        HIPCHK(hipMemcpyAsync((void *)A.fl, flags + pos, (size_t)m * 4, hipMemcpyHostToDevice, d->stream));
+        if (idx) HIPCHK(hipMemcpyAsync((void *)A.idx, idx + pos, (size_t)m * 4, hipMemcpyHostToDevice, d->stream));
+        A.first = first + pos; A.n = m; A.pos0 = pos;
+        A.B = m >= (1u << 18) ? 4u : 1u;                             // four starts share a thread's inversion once the launch fills the GPU without
+        A.TT = ((m + A.B - 1) / A.B + 255u) / 256u * 256u;
+        hipLaunchKernelGGL(kangaroo_seed_kernel, dim3(A.TT / 256u), dim3(256), SEED_LDS, d->stream, A);
+        HIPCHK(hipGetLastError());
+    }
+    uint32_t out[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(out, k->seed_out, 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (n_infinite) *n_infinite = out[0];
+    if (first_infinite) *first_infinite = out[0] ? out[1] : 0u;
+    return BSGS_OK;
+}

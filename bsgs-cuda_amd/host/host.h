@@ -224,6 +224,9 @@ void gpu_thread(Job *J, int gpu, int slot, bsgs_dev *dev);
 int selftest(int argc, char **argv);
 // the lines a found key is reported with (1_9_7File.pb:5146-5160): returns the win.txt text, `console` receives the console block
 std::string key_lines(int listpos, const Scalar &key, const Affine &pub, std::string &console);
-// host_kangaroo.cpp: bsgs_mi355x -kangaroo, and -selftest kangaroo (the table of distinguished points on a scripted record stream)
+// host_kangaroo.cpp: bsgs_mi355x -kangaroo, -selftest kangaroo (the table of distinguished points on a scripted record stream), and the work file's
+// selftests kangaroo-work / kangaroo-table-roundtrip
 int kangaroo_main(int argc, char **argv);
 int kangaroo_selftest(const std::vector<std::string> &args);
+int kangaroo_work_selftest(const std::vector<std::string> &args);
+int kangaroo_roundtrip_selftest(const std::vector<std::string> &args);

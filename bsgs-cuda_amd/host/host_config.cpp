@@ -67,10 +67,15 @@ void usage(const Config &c)
            "-w auto      The table Tune picks for the range given: the one that minimises table build + worst-case search (a 64-bit range: -w 30 -ext)\n"
            "-buckets     Extended table: the number of buckets itself (any number below 2^32; 64-byte lines up to 12.5 items per bucket, else 128-byte lines), e.g. -w 35 -buckets 3221225472\n",
            c.t, c.b, c.p, c.pk.c_str(), c.htsz, c.wt);
-    printf("-kangaroo    Pollard's kangaroo search of one public key (-pb) in [-pk, -pke], 2^20 <= width <= 2^125, no baby table; with -d, -dir (not with -w -htsz -infile -wl -onlygen)\n"
+    printf("-kangaroo    Pollard's kangaroo search of one public key (-pb) in [-pk, -pke], 2^20 <= width <= 2^125, no baby table; with -d, -dir, -wl, -wt (not with -w -htsz -infile -onlygen)\n"
            "-dp N        Kangaroo: distinguished points have the top N bits of x zero (0..32; default chosen from the range)\n"
            "-kn N        Kangaroo: kangaroos per engine (default chosen from the range)\n"
-           "-kseed S     Kangaroo: seed of the herds and the jump table (default: random, printed)\n");
+           "-kseed S     Kangaroo: seed of the herds and the jump table (default: random, printed)\n"
+           "-wt N        Kangaroo: the whole search (table of distinguished points, herds, counters) is saved to <dir>/kangaroo.work every N seconds (default 180, at least 30),\n"
+           "             and once more when the run stops without the key; the file is removed when the key is found\n"
+           "-wl FILE     Kangaroo: continue from a kangaroo.work file: same -pb -pk -pke and number of -d entries; -dp -kn -kseed are taken from the file\n"
+           "-ksteps N    Kangaroo: stop once N steps were walked in total (checked after each launch), save kangaroo.work, exit code 3 (SIGINT / SIGTERM do the same)\n"
+           "-kcpuseed    Kangaroo: compute the kangaroos' start points on the host CPU instead of the GPU (same herd; for cross-checks)\n");
 }
 
 Config parse_args(int argc, char **argv)

@@ -135,6 +135,10 @@ int selftest(int argc, char **argv)
                 J.inflight.push_back(v); J.inflight_valid.push_back(valid);
             }
             save_checkpoint(R.cfg, J.listpos, "selftest", J.checkpoint_counter());
+        } else if (a[i] == "kangaroo-work") {                               // the header of a work file (host_kangaroo.cpp)
+            return kangaroo_work_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-table-roundtrip") {                    // the table through a work file in the middle of a record stream
+            return kangaroo_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo") {                                    // the rest of the command line: range, public key, record stream (host_kangaroo.cpp)
             return kangaroo_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "joblist" && i + 1 < a.size()) {                  // the rest of the command line is the script

@@ -27,7 +27,7 @@ NATIVE_SYMBOLS = [
     "bsgs_tiles_per_launch", "bsgs_engine_geometry", "bsgs_run_digest", "bsgs_selftest_lo64", "bsgs_compat_stats", "bsgs_debug_buffers", "bsgs_alloc_stats", "bsgs_tune_placement", "bsgs_chain_placement", "bsgs_chain_grades", "bsgs_debug_grade_rule", "bsgs_debug_xcd_profile",
     "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
-    "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry",
+    "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc"]
@@ -173,6 +173,7 @@ def lib():
             "bsgs_kangaroo_download": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
             "bsgs_kangaroo_run": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
             "bsgs_kangaroo_geometry": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+            "bsgs_kangaroo_seed": [vp, u8p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         }
         for name, args in sig.items():
             fn = getattr(L, name, None)
@@ -651,6 +652,18 @@ class Device:
         out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step}
                for r in recs[:n.value]]
         return out, dropped.value, ms.value
+
+    def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):
+        """start points on the GPU: kangaroo idx[k] (first + k without idx) := (d*G or Q + d*G, d, flags[k]) for d = offsets[k] (a signed integer) and
+        flags[k] = 0 or KANGAROO_WILD; Q = (x, y) or None when no entry is wild.  -> (starts at infinity, lowest position of one)"""
+        n = len(offsets)
+        assert len(flags) == n and (idx is None or len(idx) == n)
+        d = b"".join((v % (1 << 128)).to_bytes(16, "little") for v in offsets)
+        q = le32(Q[0]) + le32(Q[1]) if Q is not None else None
+        ninf, first_inf = C.c_uint32(), C.c_uint32()
+        _chk(self.L.bsgs_kangaroo_seed(self.h, q, (C.c_uint32 * n)(*idx) if idx is not None else None, first, n, d, (C.c_uint32 * n)(*flags), C.byref(ninf),
+                                       C.byref(first_inf)))
+        return ninf.value, first_inf.value
 
     def kangaroo_geometry(self):
         t, g, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
