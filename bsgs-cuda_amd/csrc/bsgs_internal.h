@@ -25,6 +25,8 @@ struct bsgs_kangaroo {
     u32x4 *seed_z = nullptr;               // the chunk's Jacobian Z, [2][cap]
     u32 *seed_out = nullptr;               // {kangaroos at infinity, lowest position of one}
     uint32_t seed_cap = 0;
+    u32x4 *mark = nullptr;                 // bsgs_kangaroo_setup_sym: the cycle check's marks, [2][N]
+    uint32_t R = 0;                        // bsgs_kangaroo_setup_sym: jump points of the symmetric walk (0: the plain walk)
 };
 
 struct bsgs_dev {

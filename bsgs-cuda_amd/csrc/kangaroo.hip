@@ -34,7 +34,8 @@ __device__ __forceinline__ void lds_fe(fe &r, const char *q)
 }
 
 // one record per lane with `hit`: vector stores, one atomic per wave (as report() in giant_kernel.hip.h); slots past the capacity are counted, not written
-__device__ __forceinline__ void kang_record(const KangArgs &A, bool hit, const fe &x, const u32x4 &d, u32 idx, u32 flags, u32 step, u32 lane)
+template <class ARGS>
+__device__ __forceinline__ void kang_record(const ARGS &A, bool hit, const fe &x, const u32x4 &d, u32 idx, u32 flags, u32 step, u32 lane)
 {
     const u64 m = __ballot(hit);
     if (m) {
@@ -157,6 +158,157 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
 }
 
+// ---- the symmetric walk (include/bsgs_hip.h, "Kangaroo, symmetric walk"): classes {P, -P}, never the same jump twice running, cycles retired by a mark ----
+// The R jump points do not fit LDS next to the inversion regions (72 KiB at R = 1024): the table stays in device memory as {x, y}[R] | s[R] and is read
+// through the caches.  The step is the plain one plus: the index rule on the flags' last index, y and d negated when the new y is odd, the flags written back
+// every step, and in the last KANG_CYCLE_WINDOW steps of a launch one 32-byte compare against the x the kangaroo had before them.
+#define KANG_LAST_VALID 0x100u
+#define KANG_LAST_SHIFT 9u
+#define KANG_LAST_MASK (0x1FFFu << 8)                       // valid bit and the 12 index bits
+
+struct KangSymArgs {
+    u32x4 *st;             // as KangArgs
+    u32 *flags;            // [N]: BSGS_KANGAROO_WILD | NEG | CYCLE | DEAD, last jump index (bit 8 valid, bits 9..20)
+    u32x4 *chain;
+    const u32x4 *table;    // {x, y}[R] (64 bytes each), then s[R]
+    u32 *rec;
+    u32x4 *mark;           // [2][N]: x after step mark_step of this launch
+    u32 N, T, G, steps, dp_mask, cap, rmask;
+    u32 mark_step;         // steps - 1 - KANG_CYCLE_WINDOW, or ~0u when the launch is too short for a check
+};
+
+__device__ __forceinline__ u32 kang_sym_index(u32 x0, u32 fl, u32 rmask)
+{
+    const u32 j = x0 & rmask;
+    return ((fl & KANG_LAST_VALID) && ((fl >> KANG_LAST_SHIFT) & 0xFFFu) == j) ? (j + 1u) & rmask : j;
+}
+
+// (y, d, flags) -> the class representative's when y is odd
+__device__ __forceinline__ void kang_sym_normalise(fe &y, u32x4 &d, u32 &fl)
+{
+    if (y.v[0] & 1u) {
+        fe_neg(y, y);
+        u32 c = 0, co;
+        d.x = __builtin_subc(0u, d.x, c, &co); c = co;
+        d.y = __builtin_subc(0u, d.y, c, &co); c = co;
+        d.z = __builtin_subc(0u, d.z, c, &co); c = co;
+        d.w = __builtin_subc(0u, d.w, c, &co);
+        if (fl & BSGS_KANGAROO_WILD) fl ^= BSGS_KANGAROO_NEG;
+    }
+}
+// kang_element on the representative: the equal-x cases compare the even one of y and p - y with J_j.y
+__device__ __forceinline__ u32 kang_sym_element(fe &e, const fe &x, const fe &jx, const fe &jy, const u32x4 *ylo, const u32x4 *yhi, u32 fl)
+{
+    if (__builtin_expect((fl & BSGS_KANGAROO_DEAD) != 0u, 0)) { fe_set_one(e); return 3u; }
+    fe_sub(e, jx, x);
+    if (__builtin_expect(!fe_is_zero(e), 1)) return 0u;
+    fe y;
+    fe_load2(y, ylo, yhi);
+    if (y.v[0] & 1u) fe_neg(y, y);
+    if (fe_eq(y, jy)) { fe_add(e, y, y); return 1u; }
+    fe_set_one(e);
+    return 2u;
+}
+
+template <bool BLOCK_INV>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) kangaroo_sym_kernel(const KangSymArgs A)
+{
+    const u32 T = A.T, N = A.N, G = A.G, rmask = A.rmask;
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;             // the launch has exactly T threads
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    u32x4 *const sx0 = A.st, *const sx1 = A.st + N, *const sy0 = A.st + 2 * (u64)N, *const sy1 = A.st + 3 * (u64)N, *const sd = A.st + 4 * (u64)N;
+    const u64 *const ts = (const u64 *)(A.table + 4 * ((u64)rmask + 1));
+    for (u32 step = 0; step < A.steps; step++) {
+        fe acc;
+        fe_set_one(acc);
+        for (u32 g = 0; g < G; g++) {
+            const u32 i = g * T + t;
+            fe x, jx, jy, e;
+            fe_load2(x, sx0 + i, sx1 + i);
+            const u32 fl = A.flags[i];
+            const u32x4 *jp = A.table + 4 * (u64)kang_sym_index(x.v[0], fl, rmask);
+            fe_load2(jx, jp, jp + 1); fe_load2(jy, jp + 2, jp + 3);
+            kang_sym_element(e, x, jx, jy, sy0 + i, sy1 + i, fl);
+            fe_mul(acc, acc, e);
+            CHAIN_STORE(A.chain + ((u64)g * 2 + 0) * T + t, A.chain + ((u64)g * 2 + 1) * T + t, acc);
+        }
+        fe inv;
+        if (BLOCK_INV) fe_inv_block<KANG_REGION, 4>(inv, acc, lane, wave, blockIdx.x & 3u);
+        else fe_inv(inv, acc);
+        for (u32 gg = 0; gg < G; gg++) {
+            const u32 g = G - 1 - gg;
+            const u32 i = g * T + t;
+            fe x, y, jx, jy, e, s;
+            fe_load2(x, sx0 + i, sx1 + i);
+            u32 fl = A.flags[i];
+            const u32 j = kang_sym_index(x.v[0], fl, rmask);
+            const u32x4 *jp = A.table + 4 * (u64)j;
+            fe_load2(jx, jp, jp + 1); fe_load2(jy, jp + 2, jp + 3);
+            const u32 kind = kang_sym_element(e, x, jx, jy, sy0 + i, sy1 + i, fl);
+            if (g > 0) {
+                fe c;
+                CHAIN_LOAD(c, A.chain + ((u64)(g - 1) * 2 + 0) * T + t, A.chain + ((u64)(g - 1) * 2 + 1) * T + t);
+                fe_mul(s, inv, c);
+                fe_mul(inv, inv, e);
+            } else {
+                s = inv;
+            }
+            u32x4 d = sd[i];
+            bool rec = false;
+            if (__builtin_expect(kind < 2u, 1)) {
+                fe_load2(y, sy0 + i, sy1 + i);
+                kang_sym_normalise(y, d, fl);                            // (a start of odd y; after a step y is even)
+                fe lam, t1, nx, x3, y3;
+                fe_neg(nx, x);
+                if (__builtin_expect(kind == 0u, 1)) {
+                    fe_sub(t1, jy, y);
+                    fe_mul(lam, t1, s);
+                    fe njx;
+                    fe_neg(njx, jx);
+                    fe_sqr_add2(x3, lam, nx, njx);
+                } else {
+                    fe_sqr(t1, x);
+                    fe_add(e, t1, t1);
+                    fe_add(t1, e, t1);
+                    fe_mul(lam, t1, s);
+                    fe_sqr_add2(x3, lam, nx, nx);
+                }
+                fe_canon(x3);
+                fe_sub(t1, x, x3);
+                fe_mul(y3, lam, t1);
+                fe_sub(y3, y3, y);
+                fe_canon(y3);
+                const u64 sj = ts[j];
+                u32 c = 0, co;
+                d.x = __builtin_addc(d.x, (u32)sj, c, &co); c = co;
+                d.y = __builtin_addc(d.y, (u32)(sj >> 32), c, &co); c = co;
+                d.z = __builtin_addc(d.z, 0u, c, &co); c = co;
+                d.w = __builtin_addc(d.w, 0u, c, &co);
+                kang_sym_normalise(y3, d, fl);
+                fl = (fl & ~KANG_LAST_MASK) | KANG_LAST_VALID | (j << KANG_LAST_SHIFT);
+                fe_store2(sx0 + i, sx1 + i, x3);
+                fe_store2(sy0 + i, sy1 + i, y3);
+                sd[i] = d;
+                x = x3;
+                rec = (x3.v[7] & A.dp_mask) == 0u;
+                if (step == A.mark_step) {
+                    fe_store2(A.mark + i, A.mark + N + i, x3);
+                } else if (step > A.mark_step) {                         // (never with mark_step = ~0u) back on the marked x: a cycle of at most the window
+                    fe m;
+                    fe_load2(m, A.mark + i, A.mark + N + i);
+                    if (__builtin_expect(fe_eq(m, x3), 0)) { fl |= BSGS_KANGAROO_DEAD | BSGS_KANGAROO_CYCLE; rec = true; }
+                }
+                A.flags[i] = fl;
+            } else if (kind == 2u) {
+                fl |= BSGS_KANGAROO_DEAD;
+                A.flags[i] = fl;
+                rec = true;
+            }
+            kang_record(A, rec, x, d, i, fl, step, lane);
+        }
+    }
+}
+
 // ---- gather / scatter of whole states (host format bsgs_kangaroo_state, 96 bytes) -------------------------------------------------------------------
 __global__ void kangaroo_scatter_kernel(u32x4 *st, u32 *flags, u32 N, const u32x4 *in, const u32 *idx, u32 first, u32 n)
 {
@@ -184,7 +336,7 @@ void bsgs_kangaroo_release(bsgs_dev *d)
     bsgs_kangaroo *k = d->kangaroo;
     if (!k) return;
     for (void *p : {(void *)k->st, (void *)k->chain, (void *)k->table, (void *)k->staging, (void *)k->flags, (void *)k->rec, (void *)k->idx, (void *)k->comb,
-                    (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out})
+                    (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out, (void *)k->mark})
         if (p) (void)hipFree(p);
     if (k->rec_host) (void)hipHostFree(k->rec_host);
     delete k;
@@ -194,38 +346,57 @@ void bsgs_kangaroo_release(bsgs_dev *d)
 static_assert(sizeof(bsgs_kangaroo_state) == 96, "state record: 96 bytes");
 static_assert(sizeof(bsgs_kangaroo_record) == 64, "DP record: 64 bytes");
 
-extern "C" int bsgs_kangaroo_setup(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t dp, uint32_t herd, uint32_t per_thread,
-                                   uint32_t record_cap)
+// the herd of both walks; n_jumps = 0: the plain walk's 64 points in its LDS layout x[64] | y[64] | s[64]; else the symmetric walk's {x, y}[R] | s[R]
+static int kangaroo_alloc(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t n_jumps, uint32_t dp, uint32_t herd, uint32_t per_thread,
+                          uint32_t record_cap)
 {
+    const uint32_t R = n_jumps ? n_jumps : KANG_NJ;
     if (!d || !jumps_xy_le || !jump_scalars) return fail(BSGS_ERR_ARG, "null");
     if (dp > 32) return fail(BSGS_ERR_ARG, "dp %u: at most 32", dp);
     if (!per_thread || !herd || herd % (64u * per_thread)) return fail(BSGS_ERR_ARG, "herd %u: a multiple of 64 * per_thread (%u)", herd, per_thread);
     if (!record_cap || record_cap > (1u << 26)) return fail(BSGS_ERR_ARG, "record capacity %u: 1..2^26", record_cap);
-    for (int j = 0; j < (int)KANG_NJ; j++) if (!jump_scalars[j]) return fail(BSGS_ERR_ARG, "jump scalar %d is zero", j);
+    for (int j = 0; j < (int)R; j++) if (!jump_scalars[j]) return fail(BSGS_ERR_ARG, "jump scalar %d is zero", j);
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipStreamSynchronize(d->stream));
     bsgs_kangaroo_release(d);
     bsgs_kangaroo *k = new bsgs_kangaroo();
     d->kangaroo = k;
-    k->N = herd; k->G = per_thread; k->T = herd / per_thread; k->dp = dp; k->cap = record_cap;
+    k->N = herd; k->G = per_thread; k->T = herd / per_thread; k->dp = dp; k->cap = record_cap; k->R = n_jumps;
     k->block = k->T % 256u == 0 ? 256u : 64u;
     HIPCHK(hipMalloc(&k->st, (size_t)herd * 5 * 16));
     HIPCHK(hipMalloc(&k->flags, (size_t)herd * 4));
     HIPCHK(hipMalloc(&k->chain, (size_t)herd * 32));
-    HIPCHK(hipMalloc(&k->table, KANG_TABLE_BYTES));
+    HIPCHK(hipMalloc(&k->table, (size_t)R * 72));
+    if (n_jumps) HIPCHK(hipMalloc(&k->mark, (size_t)herd * 32));
     HIPCHK(hipMalloc(&k->rec, KANG_REC_HEADER + (size_t)record_cap * 64));
     HIPCHK(hipHostMalloc(&k->rec_host, (size_t)record_cap * 64, hipHostMallocDefault));
     HIPCHK(hipMemsetAsync(k->st, 0, (size_t)herd * 5 * 16, d->stream));
     HIPCHK(hipMemsetAsync(k->flags, 0xFF, (size_t)herd * 4, d->stream));         // every kangaroo dead until its state is uploaded
-    std::vector<uint8_t> tab(KANG_TABLE_BYTES);
-    for (uint32_t j = 0; j < KANG_NJ; j++) {
-        memcpy(&tab[j * 32], jumps_xy_le + j * 64, 32);
-        memcpy(&tab[KANG_NJ * 32 + j * 32], jumps_xy_le + j * 64 + 32, 32);
-        memcpy(&tab[KANG_NJ * 64 + j * 8], &jump_scalars[j], 8);
+    if (n_jumps) HIPCHK(hipMemsetAsync(k->mark, 0, (size_t)herd * 32, d->stream));
+    std::vector<uint8_t> tab((size_t)R * 72);
+    for (uint32_t j = 0; j < R; j++) {
+        if (n_jumps) memcpy(&tab[j * 64], jumps_xy_le + j * 64, 64);
+        else {
+            memcpy(&tab[j * 32], jumps_xy_le + j * 64, 32);
+            memcpy(&tab[R * 32 + j * 32], jumps_xy_le + j * 64 + 32, 32);
+        }
+        memcpy(&tab[R * 64 + j * 8], &jump_scalars[j], 8);
     }
     HIPCHK(hipMemcpyAsync(k->table, tab.data(), tab.size(), hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     return BSGS_OK;
+}
+extern "C" int bsgs_kangaroo_setup(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t dp, uint32_t herd, uint32_t per_thread,
+                                   uint32_t record_cap)
+{
+    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, 0, dp, herd, per_thread, record_cap);
+}
+extern "C" int bsgs_kangaroo_setup_sym(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t n_jumps, uint32_t dp, uint32_t herd,
+                                       uint32_t per_thread, uint32_t record_cap)
+{
+    if (n_jumps < 64u || n_jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (n_jumps & (n_jumps - 1u)))
+        return fail(BSGS_ERR_ARG, "%u jump points: a power of two, 64..%u", n_jumps, BSGS_KANGAROO_SYM_MAX_JUMPS);
+    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, n_jumps, dp, herd, per_thread, record_cap);
 }
 
 static int kangaroo_put(bsgs_dev *d, const uint32_t *idx, uint32_t first, uint32_t n, const bsgs_kangaroo_state *states)
@@ -293,7 +464,14 @@ extern "C" int bsgs_kangaroo_run(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_reco
     A.dp_mask = k->dp ? ~0u << (32u - k->dp) : 0u;
     HIPCHK(hipMemsetAsync(k->rec, 0, KANG_REC_HEADER, d->stream));
     HIPCHK(hipEventRecord(d->ev0, d->stream));
-    if (k->block == 256u) hipLaunchKernelGGL(kangaroo_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_LDS, d->stream, A);
+    if (k->R) {
+        KangSymArgs S;
+        S.st = k->st; S.flags = k->flags; S.chain = k->chain; S.table = k->table; S.rec = k->rec; S.mark = k->mark;
+        S.N = k->N; S.T = k->T; S.G = k->G; S.steps = steps; S.dp_mask = A.dp_mask; S.cap = k->cap; S.rmask = k->R - 1u;
+        S.mark_step = steps > BSGS_KANGAROO_CYCLE_WINDOW ? steps - 1u - BSGS_KANGAROO_CYCLE_WINDOW : ~0u;
+        if (k->block == 256u) hipLaunchKernelGGL(kangaroo_sym_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_TABLE_OFF, d->stream, S);
+        else hipLaunchKernelGGL(kangaroo_sym_kernel<false>, dim3(k->T / 64u), dim3(64), 0, d->stream, S);
+    } else if (k->block == 256u) hipLaunchKernelGGL(kangaroo_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_LDS, d->stream, A);
     else hipLaunchKernelGGL(kangaroo_kernel<false>, dim3(k->T / 64u), dim3(64), KANG_LDS, d->stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(d->ev1, d->stream));

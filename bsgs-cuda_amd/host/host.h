@@ -230,3 +230,5 @@ int kangaroo_main(int argc, char **argv);
 int kangaroo_selftest(const std::vector<std::string> &args);
 int kangaroo_work_selftest(const std::vector<std::string> &args);
 int kangaroo_roundtrip_selftest(const std::vector<std::string> &args);
+int kangaroo_sym_selftest(const std::vector<std::string> &args);                 // -selftest kangaroo-sym: the symmetric walk's table
+int kangaroo_sym_roundtrip_selftest(const std::vector<std::string> &args);       // -selftest kangaroo-sym-roundtrip: through a version-2 work file

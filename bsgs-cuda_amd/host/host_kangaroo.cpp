@@ -4,6 +4,8 @@
 // writes it.  Start points come from the GPU (bsgs_kangaroo_seed; -kcpuseed: the host's comb).  The whole search is saved to <dir>/kangaroo.work every -wt
 // seconds and when a run stops without the key, and -wl continues from such a file (layout and consistency rule: DESIGN.md 10).  -selftest kangaroo drives
 // the table with a scripted record stream and no GPU; -selftest kangaroo-work / kangaroo-table-roundtrip do the same for the work file.
+// -ksym runs the symmetric walk (the negation map; include/bsgs_hip.h "Kangaroo, symmetric walk"): offsets counted from the middle of the range, R jump points
+// (-kjumps) of mean -kjumpscale * N_k sqrt(W) / 4, the collision rule with signs, cycles counted, a version-2 work file; -selftest kangaroo-sym / kangaroo-sym-roundtrip.
 #include "host.h"
 
 #include <csignal>
@@ -29,6 +31,26 @@ i128 herd_offset(uint64_t &state, u128 W, bool wild)
 {
     const u128 r = draw128(state);
     return wild ? (i128)(r % W) - (i128)(W / 2) : (i128)(1 + r % (W - 1));
+}
+// -ksym (tests/kangaroo_sym_model.py herd_offset): tame uniform in [0, W/2), wild uniform in [-W/4, W/4), the same stream
+i128 herd_offset_sym(uint64_t &state, u128 W, bool wild)
+{
+    u128 r = draw128(state) % (W / 2);
+    while (!wild && !r) r = draw128(state) % (W / 2);                 // a tame kangaroo at 0 would stand on the point at infinity: the next draw
+    return wild ? (i128)r - (i128)(W / 4) : (i128)r;
+}
+// v / 2 mod n
+Scalar sc_half(Scalar v)
+{
+    uint64_t top = 0;
+    if (v.l[0] & 1) {
+        unsigned __int128 c = 0;
+        for (int i = 0; i < 4; i++) { c += (unsigned __int128)v.l[i] + hs::SC_N.l[i]; v.l[i] = (uint64_t)c; c >>= 64; }
+        top = (uint64_t)c;
+    }
+    for (int i = 0; i < 3; i++) v.l[i] = (v.l[i] >> 1) | (v.l[i + 1] << 63);
+    v.l[3] = (v.l[3] >> 1) | (top << 63);
+    return v;
 }
 Scalar sc_from_i128(i128 v) { return v >= 0 ? hs::sc_from_u128((u128)v) : hs::sc_neg(hs::sc_from_u128((u128)-v)); }
 bool parse_hex128(const std::string &s, u128 &v)
@@ -87,17 +109,24 @@ bsgs_kangaroo_state to_state(const Affine &p, i128 d, bool wild)
 class KangarooTable {
 public:
     enum Verdict { NEW, FOUND, RESEED, FALSE_MATCH, REPEAT };
-    KangarooTable(const Scalar &a, u128 W, const Affine &P) : a_(a), W_(W), P_(P) { map_.reserve(1u << 20); }
+    // sym: the rule of the symmetric walk (include/bsgs_hip.h "Kangaroo, symmetric walk"; tests/kangaroo_sym_model.py SymTable)
+    KangarooTable(const Scalar &a, u128 W, const Affine &P, bool sym = false) : a_(a), W_(W), P_(P), sym_(sym)
+    {
+        map_.reserve(1u << 20);
+        mid_ = hs::sc_add(a, hs::sc_from_u128(W / 2));
+        hi_ = hs::sc_add(a, hs::sc_from_u128(W - 1));
+    }
     // one record: FOUND (*key = k), RESEED (the record's kangaroo follows another of its type, or died), FALSE_MATCH (tame and wild x agree in the key but the
     // difference does not solve: counted, ignored), REPEAT (the same kangaroo's own point again), NEW (stored)
     Verdict add(const uint8_t x[32], u128 d, uint32_t kid, uint32_t flags, Scalar *key)
     {
-        if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; return RESEED; }
+        if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; if (flags & BSGS_KANGAROO_CYCLE) cycles_++; return RESEED; }
         uint64_t k64;
         memcpy(&k64, x, 8);
+        if (sym_) return add_sym(k64, d, kid, flags, key);
         const bool wild = flags & BSGS_KANGAROO_WILD;
         auto it = map_.find(k64);
-        if (it == map_.end()) { map_.emplace(k64, Entry{d, kid, wild}); return NEW; }
+        if (it == map_.end()) { map_.emplace(k64, Entry{d, kid, wild, false}); return NEW; }
         const Entry &e = it->second;
         if (e.wild == wild) {
             if (e.kid == kid) return REPEAT;
@@ -116,12 +145,14 @@ public:
     size_t size() const { return map_.size(); }
     uint64_t false_matches() const { return false_; }
     uint64_t reseeds() const { return reseeds_; }
+    uint64_t cycles() const { return cycles_; }
+    void set_cycles(uint64_t c) { cycles_ = c; }
     // the work file's view: one 32-byte entry per stored point -- low 64 bits of x, d, kangaroo, type (0 tame, 1 wild) -- and the two counters
     void write_entries(std::vector<uint8_t> &out) const
     {
         for (const auto &kv : map_) {
             uint8_t e[32];
-            const uint32_t type = kv.second.wild ? 1u : 0u;
+            const uint32_t type = (kv.second.wild ? 1u : 0u) | (kv.second.neg ? 2u : 0u);       // (version 2: 3 = a wild kangaroo with NEG)
             memcpy(e, &kv.first, 8); memcpy(e + 8, &kv.second.d, 16); memcpy(e + 24, &kv.second.kid, 4); memcpy(e + 28, &type, 4);
             out.insert(out.end(), e, e + 32);
         }
@@ -132,28 +163,61 @@ public:
             const uint8_t *e = entries + 32 * i;
             uint64_t k64; Entry en; uint32_t type;
             memcpy(&k64, e, 8); memcpy(&en.d, e + 8, 16); memcpy(&en.kid, e + 24, 4); memcpy(&type, e + 28, 4);
-            if (type > 1u) return false;
-            en.wild = type == 1u;
+            if (type > 1u && !(sym_ && type == 3u)) return false;
+            en.wild = type & 1u; en.neg = type == 3u;
             if (!map_.emplace(k64, en).second) return false;
         }
         false_ = false_matches; reseeds_ = reseeds;
         return true;
     }
 private:
-    struct Entry { u128 d; uint32_t kid; bool wild; };
+    struct Entry { u128 d; uint32_t kid; bool wild, neg; };
+    // a record's point is sigma Q + d G, sigma = 0 tame, +1 wild, -1 wild with NEG; equal x: sigma1 Q + d1 G = +-(sigma2 Q + d2 G), so for each sign with
+    // sigma1 -+ sigma2 != 0 the candidate is k'' = (+-d2 - d1) / (sigma1 -+ sigma2) mod n (the divisor is +-1 or +-2), the key a + W/2 + k''
+    Verdict add_sym(uint64_t k64, u128 d, uint32_t kid, uint32_t flags, Scalar *key)
+    {
+        const bool wild = flags & BSGS_KANGAROO_WILD, neg = wild && (flags & BSGS_KANGAROO_NEG);
+        auto it = map_.find(k64);
+        if (it == map_.end()) { map_.emplace(k64, Entry{d, kid, wild, neg}); return NEW; }
+        const Entry &e = it->second;
+        if (e.kid == kid) return REPEAT;
+        const int s1 = e.wild ? (e.neg ? -1 : 1) : 0, s2 = wild ? (neg ? -1 : 1) : 0;
+        const Scalar d1 = sc_from_i128((i128)e.d), d2 = sc_from_i128((i128)d);
+        bool tried = false;
+        for (int sign = 1; sign >= -1; sign -= 2) {
+            const int den = s1 - sign * s2;
+            if (!den) continue;
+            tried = true;
+            Scalar k = hs::sc_sub(sign > 0 ? d2 : hs::sc_neg(d2), d1);
+            if (den == 2 || den == -2) k = sc_half(k);
+            if (den < 0) k = hs::sc_neg(k);
+            const Scalar cand = hs::sc_add(mid_, k);
+            if (hs::fe_cmp(cand, a_) < 0 || hs::fe_cmp(cand, hi_) > 0) continue;
+            const Affine q = hs::point_mul(hs::G, cand);
+            if (!q.inf && hs::fe_equal(q.x, P_.x) && hs::fe_equal(q.y, P_.y)) { *key = cand; return FOUND; }
+        }
+        if (tried) false_++;
+        reseeds_++;
+        return RESEED;
+    }
     const Scalar a_;
     const u128 W_;
     const Affine P_;
+    const bool sym_;
+    Scalar mid_, hi_;
     std::unordered_map<uint64_t, Entry> map_;
-    uint64_t false_ = 0, reseeds_ = 0;
+    uint64_t false_ = 0, reseeds_ = 0, cycles_ = 0;
 };
 
 // ---- the work file <dir>/kangaroo.work (DESIGN.md 10 states the layout byte by byte; tests/test_kangaroo_work.py parses it) -------------------------
 namespace {
 const char WORK_MAGIC[8] = {'K', 'A', 'N', 'G', 'W', 'O', 'R', 'K'};
-const uint32_t WORK_VERSION = 1;
-const size_t WORK_HEADER = 144;
+const uint32_t WORK_VERSION = 1, WORK_VERSION_SYM = 2;       // 2: written and read by -ksym only; the header continues behind the fingerprint
+const size_t WORK_HEADER = 144, WORK_HEADER_SYM = 168;        // version 2: + jump points (u32), zero (u32), jump scale (f64), cycles retired (u64)
 struct WorkHeader {
+    uint32_t version = WORK_VERSION, jumps = 0;
+    double jumpscale = 0.0;
+    uint64_t cycles = 0;
     uint32_t engines = 0, dp = 0, per_thread = 0;
     uint64_t herd = 0, seed = 0, rng = 0, steps = 0, dps = 0, dropped = 0, false_matches = 0, reseeds = 0, table = 0;
     double elapsed = 0.0;
@@ -170,16 +234,22 @@ std::string kangaroo_fingerprint(const Affine &P, const Scalar &lo, const Scalar
 {
     std::ostringstream s;
     s << hs::compress_pubkey(P) << hs::fe_to_hex(lo) << hs::fe_to_hex(hi) << "dp" << h.dp << "kn" << h.herd << "g" << h.per_thread << "e" << h.engines << "s" << h.seed;
+    if (h.version == WORK_VERSION_SYM) {
+        char js[40];
+        snprintf(js, sizeof js, "%.17g", h.jumpscale);
+        s << "sym1" << "r" << h.jumps << "js" << js;
+    }
     return sha1_hex(s.str());
 }
 void put_header(std::vector<uint8_t> &b, const WorkHeader &h)
 {
-    b.assign(WORK_HEADER, 0);
+    b.assign(h.version == WORK_VERSION_SYM ? WORK_HEADER_SYM : WORK_HEADER, 0);
     memcpy(&b[0], WORK_MAGIC, 8);
-    memcpy(&b[8], &WORK_VERSION, 4); memcpy(&b[12], &h.engines, 4); memcpy(&b[16], &h.herd, 8); memcpy(&b[24], &h.dp, 4); memcpy(&b[28], &h.per_thread, 4);
+    memcpy(&b[8], &h.version, 4); memcpy(&b[12], &h.engines, 4); memcpy(&b[16], &h.herd, 8); memcpy(&b[24], &h.dp, 4); memcpy(&b[28], &h.per_thread, 4);
     memcpy(&b[32], &h.seed, 8); memcpy(&b[40], &h.rng, 8); memcpy(&b[48], &h.steps, 8); memcpy(&b[56], &h.dps, 8); memcpy(&b[64], &h.dropped, 8);
     memcpy(&b[72], &h.false_matches, 8); memcpy(&b[80], &h.reseeds, 8); memcpy(&b[88], &h.elapsed, 8); memcpy(&b[96], &h.table, 8);
     memcpy(&b[104], h.fingerprint.data(), std::min<size_t>(40, h.fingerprint.size()));
+    if (h.version == WORK_VERSION_SYM) { memcpy(&b[144], &h.jumps, 4); memcpy(&b[152], &h.jumpscale, 8); memcpy(&b[160], &h.cycles, 8); }
 }
 // written under kangaroo.temp and renamed, as save_checkpoint does; herds by pointer: they are the large part
 bool write_work(const std::string &dst, const std::string &tmp, const WorkHeader &h, const std::vector<uint8_t> &table,
@@ -203,8 +273,9 @@ bool write_work(const std::string &dst, const std::string &tmp, const WorkHeader
     }
     return rename(tmp.c_str(), dst.c_str()) == 0;
 }
-// "" when the file is a complete work file of this version, else what is wrong with it; with_body = false reads the header and checks the sections' sizes only
-std::string read_work(const std::string &path, WorkFile &w, bool with_body)
+// "" when the file is a complete work file of version `want` (0: of either version), else what is wrong with it; with_body = false reads the header and checks
+// the sections' sizes only
+std::string read_work(const std::string &path, WorkFile &w, bool with_body, uint32_t want = WORK_VERSION)
 {
     std::ifstream f(path, std::ios::binary | std::ios::ate);
     if (!f) return "cannot open " + path;
@@ -215,14 +286,25 @@ std::string read_work(const std::string &path, WorkFile &w, bool with_body)
     if (memcmp(b, WORK_MAGIC, 8) != 0) return path + " is not a kangaroo work file";
     uint32_t version;
     memcpy(&version, &b[8], 4);
-    if (version != WORK_VERSION) return path + " has work file version " + std::to_string(version) + ", this host reads version " + std::to_string(WORK_VERSION);
+    if (want ? version != want : (version != WORK_VERSION && version != WORK_VERSION_SYM))
+        return path + " has work file version " + std::to_string(version) + ", this host reads version " + (want ? std::to_string(want) : "1 or 2");
     WorkHeader &h = w.h;
+    h.version = version;
+    const uint64_t header = version == WORK_VERSION_SYM ? WORK_HEADER_SYM : WORK_HEADER;
+    if (version == WORK_VERSION_SYM) {
+        uint8_t x[WORK_HEADER_SYM - WORK_HEADER];
+        uint32_t zero;
+        if (size < header || !f.read((char *)x, sizeof x)) return path + " is shorter than a work file's header";
+        memcpy(&h.jumps, &x[0], 4); memcpy(&zero, &x[4], 4); memcpy(&h.jumpscale, &x[8], 8); memcpy(&h.cycles, &x[16], 8);
+        if (zero || h.jumps < 64 || h.jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (h.jumps & (h.jumps - 1)) || !(h.jumpscale > 0.0) || !std::isfinite(h.jumpscale))
+            return path + ": header fields out of range";
+    }
     memcpy(&h.engines, &b[12], 4); memcpy(&h.herd, &b[16], 8); memcpy(&h.dp, &b[24], 4); memcpy(&h.per_thread, &b[28], 4);
     memcpy(&h.seed, &b[32], 8); memcpy(&h.rng, &b[40], 8); memcpy(&h.steps, &b[48], 8); memcpy(&h.dps, &b[56], 8); memcpy(&h.dropped, &b[64], 8);
     memcpy(&h.false_matches, &b[72], 8); memcpy(&h.reseeds, &b[80], 8); memcpy(&h.elapsed, &b[88], 8); memcpy(&h.table, &b[96], 8);
     h.fingerprint.assign((const char *)&b[104], 40);
     if (h.engines > 64 || h.herd > (1ull << 26) || h.dp > 32 || h.table > (1ull << 32)) return path + ": header fields out of range";
-    uint64_t pos = WORK_HEADER + 32 * h.table;
+    uint64_t pos = header + 32 * h.table;
     if (pos > size) return path + " is truncated (table)";
     if (with_body) {
         w.table.resize(32 * h.table);
@@ -257,20 +339,22 @@ bool parse_range_pub(const std::string &pk, const std::string &pke, const std::s
     W = (((u128)w.l[1] << 64) | w.l[0]) + 1;
     return true;
 }
-// one scripted record (T|W|D,<x hex>,<d hex>,<kangaroo>) into the table: prints the verdict line of -selftest kangaroo
-bool scripted_record(KangarooTable &tab, const std::string &rec)
+// one scripted record (T|W|D,<x hex>,<d hex>,<kangaroo>; sym: also N, a wild kangaroo with NEG, and C, a cycle's dead record) into the table: prints the
+// verdict line of -selftest kangaroo
+bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = false)
 {
     std::vector<std::string> f;
     std::stringstream ss(rec);
     std::string tok;
     while (std::getline(ss, tok, ',')) f.push_back(tok);
-    if (f.size() != 4 || f[0].size() != 1 || !strchr("TWD", f[0][0])) return false;
+    if (f.size() != 4 || f[0].size() != 1 || !strchr(sym ? "TWDNC" : "TWD", f[0][0])) return false;
     Scalar x;
     u128 d;
     if (!hs::fe_from_hex(x, f[1]) || !parse_hex128(f[2], d)) return false;
     uint8_t xb[32];
     hs::fe_to_le(x, xb);
-    const uint32_t flags = f[0] == "W" ? BSGS_KANGAROO_WILD : f[0] == "D" ? BSGS_KANGAROO_DEAD : 0u;
+    const uint32_t flags = f[0] == "W" ? BSGS_KANGAROO_WILD : f[0] == "D" ? BSGS_KANGAROO_DEAD : f[0] == "N" ? BSGS_KANGAROO_WILD | BSGS_KANGAROO_NEG :
+                           f[0] == "C" ? BSGS_KANGAROO_DEAD | BSGS_KANGAROO_CYCLE : 0u;
     Scalar key;
     switch (tab.add(xb, d, (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, &key)) {
     case KangarooTable::NEW: printf("new\n"); break;
@@ -296,15 +380,30 @@ int kangaroo_selftest(const std::vector<std::string> &a)
     return 0;
 }
 
+// -selftest kangaroo-sym <pk hex> <pke hex> <pubkey> <record>...: as -selftest kangaroo through the symmetric table (record types T, W, N, D, C); the summary
+// line is "summary <stored> <false matches> <reseeds> <cycles>".
+int kangaroo_sym_selftest(const std::vector<std::string> &a)
+{
+    if (a.size() < 3) return 2;
+    Scalar lo, hi; Affine P; u128 W;
+    if (!parse_range_pub(a[0], a[1], a[2], lo, hi, P, W)) return 2;
+    KangarooTable tab(lo, W, P, true);
+    for (size_t i = 3; i < a.size(); i++) if (!scripted_record(tab, a[i], true)) return 2;
+    printf("summary %zu %llu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds(), (unsigned long long)tab.cycles());
+    return 0;
+}
+
 // -selftest kangaroo-work <file> [<pk hex> <pke hex> <pubkey>]: the header of a work file, one "key value" per line, no GPU.  A file that is not a complete
-// work file ends with rc 1.  With the range and the public key the settings fingerprint is recomputed from them and the header's plan: "fingerprint-check ok",
+// work file ends with rc 1.  A version-2 file (-ksym) prints "version", "jumps", "jumpscale" and "cycles" first.  With the range and the public key the settings fingerprint is recomputed from them and the header's plan: "fingerprint-check ok",
 // or the resume path's refusal and rc 1.
 int kangaroo_work_selftest(const std::vector<std::string> &a)
 {
     if (a.size() != 1 && a.size() != 4) return 2;
     WorkFile w;
-    const std::string bad = read_work(a[0], w, false);
+    const std::string bad = read_work(a[0], w, false, 0);
     if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
+    if (w.h.version == WORK_VERSION_SYM)
+        printf("version %u\njumps %u\njumpscale %.17g\ncycles %llu\n", w.h.version, w.h.jumps, w.h.jumpscale, (unsigned long long)w.h.cycles);
     printf("steps %llu\ndps %llu\ntable %llu\nengines %u\nherd %llu\nfingerprint %s\nrng 0x%llx\n", (unsigned long long)w.h.steps, (unsigned long long)w.h.dps,
            (unsigned long long)w.h.table, w.h.engines, (unsigned long long)w.h.herd, w.h.fingerprint.c_str(), (unsigned long long)w.h.rng);
     if (a.size() == 4) {
@@ -319,7 +418,11 @@ int kangaroo_work_selftest(const std::vector<std::string> &a)
 // -selftest kangaroo-table-roundtrip <pk hex> <pke hex> <pubkey> <split> <record>...: the first <split> records into a table, the table into a work file
 // without herds (a temporary file; BSGS_SELFTEST_WORK names a path to write and keep instead), the file into a fresh table, the other records into that one.
 // Prints what -selftest kangaroo prints for the undivided stream.
-int kangaroo_roundtrip_selftest(const std::vector<std::string> &a)
+static int roundtrip_selftest(const std::vector<std::string> &a, bool sym);
+int kangaroo_roundtrip_selftest(const std::vector<std::string> &a) { return roundtrip_selftest(a, false); }
+// -selftest kangaroo-sym-roundtrip: the same through the symmetric table and a version-2 file (1024 jump points, jump scale 1); summary as -selftest kangaroo-sym
+int kangaroo_sym_roundtrip_selftest(const std::vector<std::string> &a) { return roundtrip_selftest(a, true); }
+static int roundtrip_selftest(const std::vector<std::string> &a, bool sym)
 {
     if (a.size() < 4) return 2;
     Scalar lo, hi; Affine P; u128 W;
@@ -336,24 +439,27 @@ int kangaroo_roundtrip_selftest(const std::vector<std::string> &a)
         path = tmpl;
     }
     {
-        KangarooTable first(lo, W, P);
-        for (size_t i = 0; i < split; i++) if (!scripted_record(first, a[4 + i])) return 2;
+        KangarooTable first(lo, W, P, sym);
+        for (size_t i = 0; i < split; i++) if (!scripted_record(first, a[4 + i], sym)) return 2;
         WorkHeader h;
+        if (sym) { h.version = WORK_VERSION_SYM; h.jumps = 1024; h.jumpscale = 1.0; h.cycles = first.cycles(); }
         std::vector<uint8_t> entries;
         first.write_entries(entries);
         h.table = first.size(); h.false_matches = first.false_matches(); h.reseeds = first.reseeds();
-        for (size_t i = 0; i < split; i++) if (a[4 + i][0] != 'D') h.dps++;
+        for (size_t i = 0; i < split; i++) if (a[4 + i][0] != 'D' && a[4 + i][0] != 'C') h.dps++;
         h.fingerprint = kangaroo_fingerprint(P, lo, hi, h);
         if (!write_work(path, path + ".temp", h, entries, {}, {})) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
     }
     WorkFile w;
-    const std::string bad = read_work(path, w, true);
+    const std::string bad = read_work(path, w, true, sym ? WORK_VERSION_SYM : WORK_VERSION);
     if (!keep) remove(path.c_str());
     if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
-    KangarooTable second(lo, W, P);
+    KangarooTable second(lo, W, P, sym);
     if (!second.restore(w.table.data(), w.h.table, w.h.false_matches, w.h.reseeds)) { fprintf(stderr, "the table section does not load\n"); return 1; }
-    for (size_t i = 4 + split; i < a.size(); i++) if (!scripted_record(second, a[i])) return 2;
-    printf("summary %zu %llu %llu\n", second.size(), (unsigned long long)second.false_matches(), (unsigned long long)second.reseeds());
+    second.set_cycles(w.h.cycles);
+    for (size_t i = 4 + split; i < a.size(); i++) if (!scripted_record(second, a[i], sym)) return 2;
+    if (sym) printf("summary %zu %llu %llu %llu\n", second.size(), (unsigned long long)second.false_matches(), (unsigned long long)second.reseeds(), (unsigned long long)second.cycles());
+    else printf("summary %zu %llu %llu\n", second.size(), (unsigned long long)second.false_matches(), (unsigned long long)second.reseeds());
     return 0;
 }
 
@@ -367,7 +473,11 @@ struct KangConfig {
     int wt = 180;                                  // -wt: seconds between two saves of kangaroo.work
     uint64_t ksteps = 0;                           // -ksteps: stop (saved, rc 3) once this many steps were walked in total
     bool cpuseed = false;                          // -kcpuseed: start points from the host's comb instead of bsgs_kangaroo_seed
+    bool sym = false;                              // -ksym: the symmetric walk (negation map)
+    uint32_t jumps = 0;                            // -kjumps: jump points of the symmetric walk (default 1024; resumed: from the work file)
+    double jumpscale = 0.0;                        // -kjumpscale: mean jump = scale * N_k sqrt(W) / 4 (default KSYM_JUMPSCALE; resumed: from the work file)
 };
+const double KSYM_JUMPSCALE = 2.0;                 // DESIGN.md 10, "jump scale": the best of the measured sweep
 
 KangConfig parse_kangaroo_args(int argc, char **argv)
 {
@@ -390,9 +500,13 @@ KangConfig parse_kangaroo_args(int argc, char **argv)
         else if (a == "-wt") c.wt = std::max(30, atoi(next().c_str()));
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
+        else if (a == "-ksym") c.sym = true;
+        else if (a == "-kjumps") { c.jumps = (uint32_t)strtoul(next().c_str(), nullptr, 10); if (c.jumps < 64 || c.jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (c.jumps & (c.jumps - 1))) die("-kjumps must be a power of two, 64..4096"); }
+        else if (a == "-kjumpscale") { c.jumpscale = atof(next().c_str()); if (!(c.jumpscale >= 1.0 / 64 && c.jumpscale <= 64.0)) die("-kjumpscale must be 1/64..64"); }
         else if (a == "-w" || a == "-htsz" || a == "-infile" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table, one public key)");
         else die("Unknown parameter with -kangaroo: " + a);
     }
+    if (!c.sym && (c.jumps || c.jumpscale != 0.0)) die("-kjumps and -kjumpscale belong to -ksym");
     return c;
 }
 
@@ -444,18 +558,20 @@ int kangaroo_main(int argc, char **argv)
     if (resume) {
         struct stat sb;
         if (stat(wl_path.c_str(), &sb) != 0 && stat((c.dir + "/" + c.wl).c_str(), &sb) == 0) wl_path = c.dir + "/" + c.wl;
-        const std::string bad = read_work(wl_path, wf, true);
+        const std::string bad = read_work(wl_path, wf, true, c.sym ? WORK_VERSION_SYM : WORK_VERSION);
         if (!bad.empty()) die("-kangaroo -wl: " + bad + " (only a kangaroo.work file can be resumed here; a BSGS recovery file is not supported in kangaroo mode)");
         // the settings: what the command line names must be what the file was made with, and the rest is taken from the file
         std::vector<std::string> dl;
         { std::stringstream ss(c.devices); std::string tok; while (std::getline(ss, tok, ',')) dl.push_back(tok); }
         if (kangaroo_fingerprint(P, lo, hi, wf.h) != wf.h.fingerprint || (c.dp >= 0 && (uint32_t)c.dp != wf.h.dp) || (c.kn && c.kn != wf.h.herd) ||
-            (c.seed_given && c.seed != wf.h.seed) || (!dl.empty() && dl.size() != wf.h.engines) || !wf.h.engines || !wf.h.herd || !wf.h.per_thread ||
+            (c.seed_given && c.seed != wf.h.seed) || (c.jumps && c.jumps != wf.h.jumps) || (c.jumpscale != 0.0 && c.jumpscale != wf.h.jumpscale) || (!dl.empty() && dl.size() != wf.h.engines) || !wf.h.engines || !wf.h.herd || !wf.h.per_thread ||
             wf.h.herd % (64ull * wf.h.per_thread))
             die("Recovery file was made with other settings");
     }
     printf("Kangaroo range [%s, %s], width 2^%.2f\n", hs::fe_to_hex(lo).c_str(), hs::fe_to_hex(hi).c_str(), std::log2(Wd));
-    const Affine Q = hs::point_add(P, hs::affine_neg(hs::point_mul(hs::G, lo)));
+    // -ksym: offsets are counted from the middle of the range, k'' = k - (a + W/2) (include/bsgs_hip.h "Kangaroo, symmetric walk")
+    const Scalar base = c.sym ? hs::sc_add(lo, hs::sc_from_u128(W / 2)) : lo;
+    const Affine Q = hs::point_add(P, hs::affine_neg(hs::point_mul(hs::G, base)));
     JobList jobs({c.pub}, Recovery(), c.dir, [](int, const std::string &, const Scalar &) {});      // win.txt as the BSGS path writes it
     { Config rc; rc.dir = c.dir; read_recovery(rc); }                                                  // (win.txt starts empty, as there: the key was not found yet)
     jobs.open_lanes(1);
@@ -491,7 +607,7 @@ int kangaroo_main(int argc, char **argv)
     pl.kn = kn;
     const double Nk = (double)kn * pl.engines;
     pl.expected = 2.0 * sqrtW + Nk * std::ldexp(1.0, (int)pl.dp);
-    pl.S = (uint32_t)std::max(8.0, std::min(1024.0, pl.expected / Nk / 8.0));
+    pl.S = (uint32_t)std::max(c.sym ? 2.0 * BSGS_KANGAROO_CYCLE_WINDOW : 8.0, std::min(1024.0, pl.expected / Nk / 8.0));   // -ksym: a launch longer than the cycle window
     const double per_launch = Nk / pl.engines * pl.S / std::ldexp(1.0, (int)pl.dp);
     pl.cap = (uint32_t)std::min<double>(1u << 22, 2.0 * per_launch + 65536.0);
     uint64_t seed = c.seed;
@@ -503,16 +619,23 @@ int kangaroo_main(int argc, char **argv)
     if (c.dp < 0 && 2.0 * sqrtW / std::ldexp(1.0, (int)pl.dp) > 67108864.0) printf("WARNING: the expected DP count exceeds 2^26 host entries even at -dp 32\n");
     WorkHeader wh;                                                     // what every save of this run shares
     wh.engines = pl.engines; wh.dp = pl.dp; wh.per_thread = pl.G; wh.herd = kn; wh.seed = seed;
+    if (c.sym) {
+        wh.version = WORK_VERSION_SYM;
+        wh.jumps = resume ? wf.h.jumps : c.jumps ? c.jumps : 1024u;
+        wh.jumpscale = resume ? wf.h.jumpscale : c.jumpscale != 0.0 ? c.jumpscale : KSYM_JUMPSCALE;
+        printf("Kangaroo: symmetric walk (negation map), %u jump points, jump scale %g\n", wh.jumps, wh.jumpscale);
+    }
     wh.fingerprint = kangaroo_fingerprint(P, lo, hi, wh);
     const std::string work_path = c.dir + "/kangaroo.work", work_tmp = c.dir + "/kangaroo.temp";
 
     // jump table: s_j uniform in [1, 2m), mean m = N_k sqrt(W) / 4 (at most 2^62): a function of the seed and the plan, never saved
     Shared sh;
     sh.rng = seed;
-    const double mean = std::max(1.0, std::min(std::ldexp(1.0, 62), Nk * sqrtW / 4.0));
-    std::vector<uint64_t> js(BSGS_KANGAROO_JUMPS);
-    std::vector<uint8_t> jxy(64 * BSGS_KANGAROO_JUMPS);
-    for (int j = 0; j < BSGS_KANGAROO_JUMPS; j++) {
+    const double mean = std::max(1.0, std::min(std::ldexp(1.0, 62), (c.sym ? wh.jumpscale : 1.0) * Nk * sqrtW / 4.0));
+    const int njumps = c.sym ? (int)wh.jumps : BSGS_KANGAROO_JUMPS;
+    std::vector<uint64_t> js(njumps);
+    std::vector<uint8_t> jxy(64 * (size_t)njumps);
+    for (int j = 0; j < njumps; j++) {
         const uint64_t span = (uint64_t)(2.0 * mean) > 1 ? (uint64_t)(2.0 * mean) - 1 : 1;
         js[j] = 1 + splitmix64(sh.rng) % span;
         const Affine J = hs::point_mul(hs::G, hs::fe_from_u64(js[j]));
@@ -528,11 +651,12 @@ int kangaroo_main(int argc, char **argv)
     sh.saved.resize(pl.engines);
     sh.engine_records.assign(pl.engines, 0);
     for (uint32_t e = 0; e < pl.engines; e++) sh.reseed_m.emplace_back(new std::mutex);
-    KangarooTable table(lo, W, P);
+    KangarooTable table(lo, W, P, c.sym);
     double elapsed_before = 0.0;
     if (resume) {
         if (!table.restore(wf.table.data(), wf.h.table, wf.h.false_matches, wf.h.reseeds)) die("-kangaroo -wl: the table section of " + wl_path + " does not load");
         std::vector<uint8_t>().swap(wf.table);
+        table.set_cycles(wf.h.cycles);
         sh.rng = wf.h.rng; sh.steps = wf.h.steps; sh.dps = wf.h.dps; sh.dropped = wf.h.dropped;
         elapsed_before = wf.h.elapsed;
         for (uint32_t e = 0; e < pl.engines; e++) sh.reseed[e] = wf.reseed[e];
@@ -541,7 +665,7 @@ int kangaroo_main(int argc, char **argv)
     const auto t0 = Clock::now();
     auto key_from_infinite_start = [&](i128 d) {                       // Q + u G = infinity: k' = -u
         std::lock_guard<std::mutex> lk(sh.rng_m);
-        sh.key = hs::sc_add(lo, sc_from_i128(-d));
+        sh.key = hs::sc_add(base, sc_from_i128(-d));
         sh.found = true; sh.stop = true;
     };
 
@@ -549,7 +673,10 @@ int kangaroo_main(int argc, char **argv)
     auto draw = [&](const std::vector<uint32_t> &idx, std::vector<i128> &d, std::vector<uint32_t> &fl) {
         d.resize(idx.size()); fl.resize(idx.size());
         std::lock_guard<std::mutex> lk(sh.rng_m);
-        for (size_t k = 0; k < idx.size(); k++) { fl[k] = idx[k] >= kn / 2 ? BSGS_KANGAROO_WILD : 0u; d[k] = herd_offset(sh.rng, W, fl[k] != 0u); }
+        for (size_t k = 0; k < idx.size(); k++) {
+            fl[k] = idx[k] >= kn / 2 ? BSGS_KANGAROO_WILD : 0u;
+            d[k] = c.sym ? herd_offset_sym(sh.rng, W, fl[k] != 0u) : herd_offset(sh.rng, W, fl[k] != 0u);
+        }
     };
     // -kcpuseed: the points on the calling thread; a wild start at infinity IS the key
     auto host_states = [&](const std::vector<i128> &d, const std::vector<uint32_t> &fl, std::vector<bsgs_kangaroo_state> &out) {
@@ -568,7 +695,7 @@ int kangaroo_main(int argc, char **argv)
     if (!resume) {
         for (uint32_t e = 0; e < pl.engines; e++) {
             offsets[e].resize(kn);
-            for (uint64_t i = 0; i < kn; i++) offsets[e][i] = herd_offset(sh.rng, W, i >= kn / 2);
+            for (uint64_t i = 0; i < kn; i++) offsets[e][i] = c.sym ? herd_offset_sym(sh.rng, W, i >= kn / 2) : herd_offset(sh.rng, W, i >= kn / 2);
         }
         if (cpuseed) {
             for (uint32_t e = 0; e < pl.engines; e++) {
@@ -608,7 +735,8 @@ int kangaroo_main(int argc, char **argv)
             sh.save_cv.notify_all();
         };
         if (bsgs_dev_open(gpus[e], &dev) != BSGS_OK) { bad("bsgs_dev_open"); leave(); return; }
-        if (bsgs_kangaroo_setup(dev, jxy.data(), js.data(), pl.dp, (uint32_t)kn, pl.G, pl.cap) != BSGS_OK) { bad("bsgs_kangaroo_setup"); leave(); return; }
+        if ((c.sym ? bsgs_kangaroo_setup_sym(dev, jxy.data(), js.data(), wh.jumps, pl.dp, (uint32_t)kn, pl.G, pl.cap)
+                   : bsgs_kangaroo_setup(dev, jxy.data(), js.data(), pl.dp, (uint32_t)kn, pl.G, pl.cap)) != BSGS_OK) { bad("bsgs_kangaroo_setup"); leave(); return; }
         if (!herds[e].empty()) {
             if (bsgs_kangaroo_upload(dev, 0, (uint32_t)kn, herds[e].data()) != BSGS_OK) { bad("bsgs_kangaroo_upload"); leave(); return; }
             std::vector<bsgs_kangaroo_state>().swap(herds[e]);
@@ -700,7 +828,7 @@ int kangaroo_main(int argc, char **argv)
     auto write_state = [&]() {
         WorkHeader h = wh;
         h.rng = sh.rng; h.steps = sh.steps.load(); h.dps = sh.dps.load(); h.dropped = sh.dropped.load();
-        h.false_matches = table.false_matches(); h.reseeds = table.reseeds(); h.table = table.size();
+        h.false_matches = table.false_matches(); h.reseeds = table.reseeds(); h.table = table.size(); h.cycles = table.cycles();
         h.elapsed = elapsed_before + since(t0);
         std::vector<uint8_t> entries;
         entries.reserve(32 * table.size());
@@ -782,6 +910,7 @@ int kangaroo_main(int argc, char **argv)
              (double)sh.steps.load(), (unsigned long long)sh.dps.load(), table.size(), (unsigned long long)sh.dropped.load(), (unsigned long long)table.false_matches(),
              (unsigned long long)table.reseeds());
     text += tail;
+    if (c.sym) text += "Symmetric walk: " + std::to_string(table.cycles()) + " cycles retired\n";
     for (uint32_t e = 0; e < pl.engines; e++) text += "Engine " + std::to_string(e) + " (GPU #" + std::to_string(gpus[e]) + "): " + std::to_string(sh.engine_records[e]) + " records\n";
     fputs(text.c_str(), stdout);                                       // one lane: the JobList leaves the console to the job (it appends win.txt)
     jobs.finish(0, text, sh.found.load(), win);

@@ -139,6 +139,10 @@ int selftest(int argc, char **argv)
             return kangaroo_work_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-table-roundtrip") {                    // the table through a work file in the middle of a record stream
             return kangaroo_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-sym") {                                // the same through the symmetric walk's table
+            return kangaroo_sym_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-sym-roundtrip") {
+            return kangaroo_sym_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo") {                                    // the rest of the command line: range, public key, record stream (host_kangaroo.cpp)
             return kangaroo_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "joblist" && i + 1 < a.size()) {                  // the rest of the command line is the script

@@ -27,7 +27,7 @@ NATIVE_SYMBOLS = [
     "bsgs_tiles_per_launch", "bsgs_engine_geometry", "bsgs_run_digest", "bsgs_selftest_lo64", "bsgs_compat_stats", "bsgs_debug_buffers", "bsgs_alloc_stats", "bsgs_tune_placement", "bsgs_chain_placement", "bsgs_chain_grades", "bsgs_debug_grade_rule", "bsgs_debug_xcd_profile",
     "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
-    "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed",
+    "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc"]
@@ -66,6 +66,7 @@ class KangarooRecord(C.Structure):
 
 
 KANGAROO_JUMPS, KANGAROO_WILD, KANGAROO_DEAD = 64, 1, 0x80000000
+KANGAROO_NEG, KANGAROO_CYCLE = 2, 4                # the symmetric walk (kangaroo_setup_sym)
 
 _lib = None
 
@@ -168,6 +169,7 @@ def lib():
             "bsgs_debug_realloc": [vp, C.c_int, C.c_uint64],
             "bsgs_debug_xcd_profile": [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
             "bsgs_kangaroo_setup": [vp, u8p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
+            "bsgs_kangaroo_setup_sym": [vp, u8p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
             "bsgs_kangaroo_upload": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
             "bsgs_kangaroo_upload_list": [vp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(KangarooState)],
             "bsgs_kangaroo_download": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
@@ -619,6 +621,14 @@ class Device:
             raise BsgsError("kangaroo_setup: %d jump points and scalars" % KANGAROO_JUMPS)
         xy = b"".join(le32(x) + le32(y) for x, y in jumps)
         _chk(self.L.bsgs_kangaroo_setup(self.h, xy, (C.c_uint64 * KANGAROO_JUMPS)(*scalars), dp, herd, per_thread, record_cap))
+        self._kang_cap = record_cap
+
+    def kangaroo_setup_sym(self, jumps, scalars, dp, herd, per_thread, record_cap):
+        """the symmetric walk (negation map): len(jumps) = R affine points, a power of two in 64..4096; the other kangaroo_* calls then run that walk"""
+        if len(jumps) != len(scalars):
+            raise BsgsError("kangaroo_setup_sym: as many scalars as jump points")
+        xy = b"".join(le32(x) + le32(y) for x, y in jumps)
+        _chk(self.L.bsgs_kangaroo_setup_sym(self.h, xy, (C.c_uint64 * len(scalars))(*scalars), len(jumps), dp, herd, per_thread, record_cap))
         self._kang_cap = record_cap
 
     @staticmethod

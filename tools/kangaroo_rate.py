@@ -2,7 +2,9 @@
 """Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
-    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--out FILE]
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024]] [--out FILE]
+
+--sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch).
 
 The starts are 65536 distinct points P0 + i*G, repeated over the herd (the walk's cost does not depend on which point a kangaroo stands on; repeats only
 make their DPs coincide)."""
@@ -18,18 +20,21 @@ sys.path.insert(0, os.path.join(ROOT, "bsgs-cuda_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import pybsgs                                     # noqa: E402
-from pybsgs.ecpy import G, add, mul               # noqa: E402
+from pybsgs.ecpy import G, add, mul, splitmix64   # noqa: E402
 
 # bytes of HBM traffic per kangaroo step (csrc/kangaroo.hip): pass 1 reads x (32) and flags (4) and writes the running product (32); pass 2 reads x, flags, the
 # previous running product, y and d (32 + 4 + 32 + 32 + 16) and writes x, y, d (80).  DP records (64 bytes each, 2^-dp of the steps) come on top.
 BYTES_PER_STEP = 32 + 4 + 32 + (32 + 4 + 32 + 32 + 16) + 80
+# the symmetric walk writes the flags back every step (4) and, per launch of S steps, writes the mark once and reads it 16 times (32 * 17 / S, added in main);
+# its jump points (72 bytes per step and pass) come from the 72 KiB table, which stays in L2
+BYTES_PER_STEP_SYM = BYTES_PER_STEP + 4
 
 
-def vgprs():
+def vgprs(sym=False):
     try:
         import spill_report
         for r in spill_report.report(tus=["kangaroo"]):
-            if "kangaroo_kernel<true>" in r["kernel"]:
+            if ("kangaroo_sym_kernel<true>" if sym else "kangaroo_kernel<true>") in r["kernel"]:
                 return r["vgprs"]
     except (SystemExit, Exception):
         return None
@@ -42,6 +47,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dp", type=int, default=16)
     ap.add_argument("--per-thread", type=int, default=16)
+    ap.add_argument("--sym", action="store_true")
+    ap.add_argument("--jumps", type=int, default=1024)
     ap.add_argument("--out")
     a = ap.parse_args()
     dev = pybsgs.Device(0)
@@ -50,7 +57,12 @@ def main():
     pybsgs._chk(L.bsgs_dev_cu_count(dev.h, C.byref(cus)))
     n = cus.value * 1024 * a.per_thread
     scal = [(0x9E3779B97F4A7C15 * (j + 1)) % (1 << 62) + 1 for j in range(64)]
-    dev.kangaroo_setup([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
+    if a.sym:
+        # scalars without additive structure: multiples of one constant satisfy s_a + s_b = s_c + s_d all over and would fill the walk with fruitless cycles
+        scal = [splitmix64(j)[1] % (1 << 62) + 1 for j in range(a.jumps)]
+        dev.kangaroo_setup_sym([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
+    else:
+        dev.kangaroo_setup([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
     distinct = 65536
     p = mul(0xC0FFEE << 60)
     one = []
@@ -77,10 +89,11 @@ def main():
         nrec += r
     wall = time.perf_counter() - t0
     steps = n * a.steps * a.launches
-    res = {"what": "kangaroo walk rate, one engine, full herd", "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp,
+    bps = BYTES_PER_STEP_SYM + 32 * 17 / a.steps if a.sym else BYTES_PER_STEP
+    res = {"what": "kangaroo walk rate, one engine, full herd" + (", symmetric walk, %d jump points" % a.jumps if a.sym else ""), "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp,
            "launches": a.launches, "steps_per_s": steps / wall, "steps_per_s_kernel": steps / (sum(kms) / 1e3), "ms_per_launch": sum(kms) / len(kms),
-           "ms_per_launch_min": min(kms), "bytes_per_step": BYTES_PER_STEP, "hbm_GBps_implied": steps * BYTES_PER_STEP / (sum(kms) / 1e3) / 1e9,
-           "records_per_launch": nrec / a.launches, "vgprs": vgprs()}
+           "ms_per_launch_min": min(kms), "bytes_per_step": bps, "hbm_GBps_implied": steps * bps / (sum(kms) / 1e3) / 1e9,
+           "records_per_launch": nrec / a.launches, "vgprs": vgprs(a.sym)}
     line = json.dumps(res)
     print(line)
     if a.out:
