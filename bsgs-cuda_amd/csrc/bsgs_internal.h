@@ -14,7 +14,7 @@ int bsgs_fail(int code, const char *fmt, ...);
     } while (0)
 #define fail bsgs_fail
 
-// kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table and the staging of bsgs_kangaroo_seed
+// kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip, kangaroo_seed_keys.hip: the comb table, the staging of a seed call and the key list
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
     u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
@@ -27,6 +27,8 @@ struct bsgs_kangaroo {
     uint32_t seed_cap = 0;
     u32x4 *mark = nullptr;                 // bsgs_kangaroo_setup_sym: the cycle check's marks, [2][N]
     uint32_t R = 0;                        // bsgs_kangaroo_setup_sym: jump points of the symmetric walk (0: the plain walk)
+    u32x4 *keys = nullptr;                 // bsgs_kangaroo_set_keys: n_keys affine points Q_k, x || y (64 bytes each)
+    uint32_t n_keys = 0;
 };
 
 struct bsgs_dev {

@@ -1,7 +1,7 @@
 // host.h -- declarations shared by the translation units of bsgs_mi355x, the C++ host of the MI355X BSGS solver (see bsgs_host.cpp for the reference
 // file:line map).  host_config.cpp: command line, limits, checkpoint; host_files.cpp: table files and the CPU-only generator; host_resolver.cpp: dispenser and hit
 // resolver; host_jobs.cpp: Job, the key list and its lanes (JobList); host_tune.cpp: Tune; host_engines.cpp: per-GPU engines (load, verify, search thread);
-// host_selftest.cpp: -selftest; bsgs_host.cpp: main and the start-up steps.
+// host_selftest.cpp: -selftest; host_kangaroo.cpp: -kangaroo; host_kangaroo_multi.cpp: -kangaroo -infile and its table for a list of keys; bsgs_host.cpp: main and the start-up steps.
 #pragma once
 #include "../../include/bsgs_hip.h"
 #include "../csrc/host_secp.h"
@@ -232,3 +232,5 @@ int kangaroo_work_selftest(const std::vector<std::string> &args);
 int kangaroo_roundtrip_selftest(const std::vector<std::string> &args);
 int kangaroo_sym_selftest(const std::vector<std::string> &args);                 // -selftest kangaroo-sym: the symmetric walk's table
 int kangaroo_sym_roundtrip_selftest(const std::vector<std::string> &args);       // -selftest kangaroo-sym-roundtrip: through a version-2 work file
+int kangaroo_multi_roundtrip_selftest(const std::vector<std::string> &args);     // -selftest kangaroo-multi-roundtrip: through a version-3 work file
+int kangaroo_multi_selftest(const std::vector<std::string> &args);               // -selftest kangaroo-multi: the table for a list of keys (host_kangaroo_multi.cpp)

@@ -67,7 +67,8 @@ void usage(const Config &c)
            "-w auto      The table Tune picks for the range given: the one that minimises table build + worst-case search (a 64-bit range: -w 30 -ext)\n"
            "-buckets     Extended table: the number of buckets itself (any number below 2^32; 64-byte lines up to 12.5 items per bucket, else 128-byte lines), e.g. -w 35 -buckets 3221225472\n",
            c.t, c.b, c.p, c.pk.c_str(), c.htsz, c.wt);
-    printf("-kangaroo    Pollard's kangaroo search of one public key (-pb) in [-pk, -pke], 2^20 <= width <= 2^125, no baby table; with -d, -dir, -wl, -wt (not with -w -htsz -infile -onlygen)\n"
+    printf("-kangaroo    Pollard's kangaroo search of a public key (-pb), or of every key of a list (-infile) with one herd, in [-pk, -pke], 2^20 <= width <= 2^125, no baby table; with -d, -dir, -wl, -wt (not with -w -htsz -onlygen;\n"
+           "             -infile: not with -pb, -ksym; saved as kangaroo.work version 3, which only -infile -wl continues)\n"
            "-dp N        Kangaroo: distinguished points have the top N bits of x zero (0..32; default chosen from the range)\n"
            "-kn N        Kangaroo: kangaroos per engine (default chosen from the range)\n"
            "-kseed S     Kangaroo: seed of the herds and the jump table (default: random, printed)\n"

@@ -6,32 +6,15 @@
 // the table with a scripted record stream and no GPU; -selftest kangaroo-work / kangaroo-table-roundtrip do the same for the work file.
 // -ksym runs the symmetric walk (the negation map; include/bsgs_hip.h "Kangaroo, symmetric walk"): offsets counted from the middle of the range, R jump points
 // (-kjumps) of mean -kjumpscale * N_k sqrt(W) / 4, the collision rule with signs, cycles counted, a version-2 work file; -selftest kangaroo-sym / kangaroo-sym-roundtrip.
-#include "host.h"
+#include "host_kangaroo.h"
 
 #include <csignal>
 #include <random>
 #include <unordered_map>
 
+using namespace kang;
 namespace {
-using Clock = std::chrono::steady_clock;
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
-uint64_t splitmix64(uint64_t &state)
-{
-    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-u128 draw128(uint64_t &state) { const uint64_t lo = splitmix64(state), hi = splitmix64(state); return ((u128)hi << 64) | lo; }
-// start offsets (tests/kangaroo_model.py herd_offset): tame t uniform in [1, W), wild u uniform in [-W/2, W/2), both from the seeded stream
-i128 herd_offset(uint64_t &state, u128 W, bool wild)
-{
-    const u128 r = draw128(state);
-    return wild ? (i128)(r % W) - (i128)(W / 2) : (i128)(1 + r % (W - 1));
-}
 // -ksym (tests/kangaroo_sym_model.py herd_offset): tame uniform in [0, W/2), wild uniform in [-W/4, W/4), the same stream
 i128 herd_offset_sym(uint64_t &state, u128 W, bool wild)
 {
@@ -52,7 +35,6 @@ Scalar sc_half(Scalar v)
     v.l[3] = (v.l[3] >> 1) | (top << 63);
     return v;
 }
-Scalar sc_from_i128(i128 v) { return v >= 0 ? hs::sc_from_u128((u128)v) : hs::sc_neg(hs::sc_from_u128((u128)-v)); }
 bool parse_hex128(const std::string &s, u128 &v)
 {
     Scalar t;
@@ -60,26 +42,6 @@ bool parse_hex128(const std::string &s, u128 &v)
     v = ((u128)t.l[1] << 64) | t.l[0];
     return true;
 }
-
-// fixed-base comb for 128-bit scalars: table[k][v] = v * 2^(8k) * G, sixteen mixed additions per point
-struct Comb {
-    std::vector<std::vector<Affine>> tab;
-    Comb()
-    {
-        Affine base = hs::G;
-        for (int k = 0; k < 16; k++) {
-            std::vector<Affine> m = hs::multiples(base, 256);              // base, 2 base, ..., 256 base
-            tab.push_back(std::vector<Affine>(m.begin(), m.end() - 1));
-            base = m.back();
-        }
-    }
-    hs::Jac mul(u128 s) const
-    {
-        hs::Jac r; r.inf = true;
-        for (int k = 0; k < 16; k++) { const unsigned v = (unsigned)(s >> (8 * k)) & 255u; if (v) r = hs::jac_add_affine(r, tab[k][v - 1]); }
-        return r;
-    }
-};
 
 // the start point of a kangaroo at offset d: d*G (tame) or Q + d*G (wild)
 std::vector<Affine> herd_points(const Comb &C, const Affine &Q, const std::vector<i128> &d, const std::vector<bool> &wild)
@@ -212,23 +174,7 @@ private:
 // ---- the work file <dir>/kangaroo.work (DESIGN.md 10 states the layout byte by byte; tests/test_kangaroo_work.py parses it) -------------------------
 namespace {
 const char WORK_MAGIC[8] = {'K', 'A', 'N', 'G', 'W', 'O', 'R', 'K'};
-const uint32_t WORK_VERSION = 1, WORK_VERSION_SYM = 2;       // 2: written and read by -ksym only; the header continues behind the fingerprint
 const size_t WORK_HEADER = 144, WORK_HEADER_SYM = 168;        // version 2: + jump points (u32), zero (u32), jump scale (f64), cycles retired (u64)
-struct WorkHeader {
-    uint32_t version = WORK_VERSION, jumps = 0;
-    double jumpscale = 0.0;
-    uint64_t cycles = 0;
-    uint32_t engines = 0, dp = 0, per_thread = 0;
-    uint64_t herd = 0, seed = 0, rng = 0, steps = 0, dps = 0, dropped = 0, false_matches = 0, reseeds = 0, table = 0;
-    double elapsed = 0.0;
-    std::string fingerprint;                       // 40 hex digits
-};
-struct WorkFile {
-    WorkHeader h;
-    std::vector<uint8_t> table;                    // 32 bytes per entry
-    std::vector<std::vector<uint8_t>> herds;       // per engine: herd * 96 bytes (bsgs_kangaroo_state)
-    std::vector<std::vector<uint32_t>> reseed;     // per engine: kangaroos waiting for a new start
-};
 // SHA-1, in the style of the BSGS fingerprint, over what a resumed run must share with the run that saved
 std::string kangaroo_fingerprint(const Affine &P, const Scalar &lo, const Scalar &hi, const WorkHeader &h)
 {
@@ -253,7 +199,7 @@ void put_header(std::vector<uint8_t> &b, const WorkHeader &h)
 }
 // written under kangaroo.temp and renamed, as save_checkpoint does; herds by pointer: they are the large part
 bool write_work(const std::string &dst, const std::string &tmp, const WorkHeader &h, const std::vector<uint8_t> &table,
-                const std::vector<const std::vector<bsgs_kangaroo_state> *> &herds, const std::vector<std::vector<uint32_t>> &reseed)
+                const std::vector<const std::vector<bsgs_kangaroo_state> *> &herds, const std::vector<std::vector<uint32_t>> &reseed, const WorkKeys *keys = nullptr)
 {
     {
         std::ofstream f(tmp, std::ios::binary);
@@ -261,6 +207,23 @@ bool write_work(const std::string &dst, const std::string &tmp, const WorkHeader
         std::vector<uint8_t> hb;
         put_header(hb, h);
         f.write((const char *)hb.data(), (std::streamsize)hb.size());
+        if (keys) {                                                    // version 3: the key list's state between header and table
+            std::vector<uint8_t> kb;
+            const uint32_t L = (uint32_t)keys->solved.size();
+            kb.insert(kb.end(), (const uint8_t *)&L, (const uint8_t *)&L + 4);
+            for (uint32_t k = 0; k < L; k++) {
+                kb.push_back(keys->solved[k]);
+                if (keys->solved[k]) { uint8_t le[32]; hs::fe_to_le(keys->key[k], le); kb.insert(kb.end(), le, le + 32); }
+            }
+            const uint64_t counts[3] = {keys->kept, keys->resolved, keys->links.size()};
+            kb.insert(kb.end(), (const uint8_t *)counts, (const uint8_t *)counts + 24);
+            for (const WorkLink &l : keys->links) {
+                uint8_t e[24];
+                memcpy(e, &l.j, 4); memcpy(e + 4, &l.k, 4); memcpy(e + 8, &l.delta, 16);
+                kb.insert(kb.end(), e, e + 24);
+            }
+            f.write((const char *)kb.data(), (std::streamsize)kb.size());
+        }
         f.write((const char *)table.data(), (std::streamsize)table.size());
         for (size_t e = 0; e < herds.size(); e++) {
             f.write((const char *)herds[e]->data(), (std::streamsize)(herds[e]->size() * sizeof(bsgs_kangaroo_state)));
@@ -286,11 +249,11 @@ std::string read_work(const std::string &path, WorkFile &w, bool with_body, uint
     if (memcmp(b, WORK_MAGIC, 8) != 0) return path + " is not a kangaroo work file";
     uint32_t version;
     memcpy(&version, &b[8], 4);
-    if (want ? version != want : (version != WORK_VERSION && version != WORK_VERSION_SYM))
-        return path + " has work file version " + std::to_string(version) + ", this host reads version " + (want ? std::to_string(want) : "1 or 2");
+    if (want ? version != want : (version != WORK_VERSION && version != WORK_VERSION_SYM && version != WORK_VERSION_KEYS))
+        return path + " has work file version " + std::to_string(version) + ", this host reads version " + (want ? std::to_string(want) : "1, 2 or 3");
     WorkHeader &h = w.h;
     h.version = version;
-    const uint64_t header = version == WORK_VERSION_SYM ? WORK_HEADER_SYM : WORK_HEADER;
+    uint64_t header = version == WORK_VERSION_SYM ? WORK_HEADER_SYM : WORK_HEADER;
     if (version == WORK_VERSION_SYM) {
         uint8_t x[WORK_HEADER_SYM - WORK_HEADER];
         uint32_t zero;
@@ -304,6 +267,39 @@ std::string read_work(const std::string &path, WorkFile &w, bool with_body, uint
     memcpy(&h.false_matches, &b[72], 8); memcpy(&h.reseeds, &b[80], 8); memcpy(&h.elapsed, &b[88], 8); memcpy(&h.table, &b[96], 8);
     h.fingerprint.assign((const char *)&b[104], 40);
     if (h.engines > 64 || h.herd > (1ull << 26) || h.dp > 32 || h.table > (1ull << 32)) return path + ": header fields out of range";
+    if (version == WORK_VERSION_KEYS) {                                // the key list's state: small, always read
+        WorkKeys &K = w.keys;
+        uint32_t L = 0;
+        if (header + 4 > size || !f.read((char *)&L, 4)) return path + " is truncated (key list)";
+        if (!L || L > BSGS_KANGAROO_MAX_KEYS) return path + ": header fields out of range";
+        header += 4;
+        K.solved.assign(L, 0); K.key.assign(L, Scalar());
+        for (uint32_t k = 0; k < L; k++) {
+            uint8_t st = 0, le[32];
+            if (header + 1 > size || !f.read((char *)&st, 1)) return path + " is truncated (key list)";
+            if (st > 1) return path + ": key " + std::to_string(k) + " has status " + std::to_string(st);
+            header += 1;
+            if (st) {
+                if (header + 32 > size || !f.read((char *)le, 32)) return path + " is truncated (key list)";
+                K.key[k] = hs::fe_from_le(le);
+                header += 32;
+            }
+            K.solved[k] = st;
+        }
+        uint64_t counts[3];
+        if (header + 24 > size || !f.read((char *)counts, 24)) return path + " is truncated (links)";
+        header += 24;
+        K.kept = counts[0]; K.resolved = counts[1];
+        if (counts[2] > (1ull << 32) || header + 24 * counts[2] > size) return path + " is truncated (links)";
+        K.links.resize(counts[2]);
+        for (WorkLink &l : K.links) {
+            uint8_t e[24];
+            if (!f.read((char *)e, 24)) return path + " is truncated (links)";
+            memcpy(&l.j, e, 4); memcpy(&l.k, e + 4, 4); memcpy(&l.delta, e + 8, 16);
+            if (l.j >= L || l.k >= L || l.j == l.k) return path + ": a link names key " + std::to_string(std::max(l.j, l.k));
+        }
+        header += 24 * counts[2];
+    }
     uint64_t pos = header + 32 * h.table;
     if (pos > size) return path + " is truncated (table)";
     if (with_body) {
@@ -367,6 +363,21 @@ bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = fals
 }
 }  // namespace
 
+bool kang::write_work_file(const std::string &dst, const std::string &tmp, const WorkHeader &h, const std::vector<uint8_t> &table,
+                           const std::vector<const std::vector<bsgs_kangaroo_state> *> &herds, const std::vector<std::vector<uint32_t>> &reseed, const WorkKeys *keys)
+{
+    return write_work(dst, tmp, h, table, herds, reseed, keys);
+}
+std::string kang::read_work_file(const std::string &path, WorkFile &w, bool with_body, uint32_t want) { return read_work(path, w, with_body, want); }
+// version 3: every public key of the list in order, the range, the plan and keys<L>
+std::string kang::keys_fingerprint(const std::vector<Affine> &P, const Scalar &lo, const Scalar &hi, const WorkHeader &h)
+{
+    std::ostringstream s;
+    for (const Affine &p : P) s << hs::compress_pubkey(p);
+    s << hs::fe_to_hex(lo) << hs::fe_to_hex(hi) << "dp" << h.dp << "kn" << h.herd << "g" << h.per_thread << "e" << h.engines << "s" << h.seed << "keys" << P.size();
+    return sha1_hex(s.str());
+}
+
 // -selftest kangaroo <pk hex> <pke hex> <pubkey> <record>...  record = T|W|D,<x hex>,<d hex: 128-bit two's complement>,<kangaroo> (D: a dead record).
 // Prints one line per record: "new", "found <key hex>", "reseed <kangaroo>", "false", "repeat"; then "summary <stored> <false matches> <reseeds>".
 int kangaroo_selftest(const std::vector<std::string> &a)
@@ -404,10 +415,25 @@ int kangaroo_work_selftest(const std::vector<std::string> &a)
     if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
     if (w.h.version == WORK_VERSION_SYM)
         printf("version %u\njumps %u\njumpscale %.17g\ncycles %llu\n", w.h.version, w.h.jumps, w.h.jumpscale, (unsigned long long)w.h.cycles);
+    if (w.h.version == WORK_VERSION_KEYS) {
+        uint32_t solved = 0;
+        for (uint8_t st : w.keys.solved) solved += st;
+        printf("version %u\nkeys %zu\nsolved %u\nlinks %zu\n", w.h.version, w.keys.solved.size(), solved, w.keys.links.size());
+    }
     printf("steps %llu\ndps %llu\ntable %llu\nengines %u\nherd %llu\nfingerprint %s\nrng 0x%llx\n", (unsigned long long)w.h.steps, (unsigned long long)w.h.dps,
            (unsigned long long)w.h.table, w.h.engines, (unsigned long long)w.h.herd, w.h.fingerprint.c_str(), (unsigned long long)w.h.rng);
     if (a.size() == 4) {
         Scalar lo, hi; Affine P; u128 W;
+        if (w.h.version == WORK_VERSION_KEYS) {                       // the public keys of the list, comma separated
+            std::vector<Affine> Ps;
+            std::stringstream ss(a[3]);
+            std::string tok;
+            while (std::getline(ss, tok, ',')) { if (!hs::parse_pubkey(P, cut_hex(tok)) || !hs::on_curve(P)) return 2; Ps.push_back(P); }
+            if (!hs::fe_from_hex(lo, a[1]) || !hs::fe_from_hex(hi, a[2])) return 2;
+            if (keys_fingerprint(Ps, lo, hi, w.h) != w.h.fingerprint) { fprintf(stderr, "Recovery file was made with other settings\n"); return 1; }
+            printf("fingerprint-check ok\n");
+            return 0;
+        }
         if (!parse_range_pub(a[1], a[2], a[3], lo, hi, P, W)) return 2;
         if (kangaroo_fingerprint(P, lo, hi, w.h) != w.h.fingerprint) { fprintf(stderr, "Recovery file was made with other settings\n"); return 1; }
         printf("fingerprint-check ok\n");
@@ -464,22 +490,10 @@ static int roundtrip_selftest(const std::vector<std::string> &a, bool sym)
 }
 
 namespace {
-struct KangConfig {
-    std::string devices, pub = Config().pub, pk = Config().pk, pke = Config().pke, dir = ".", wl;
-    int dp = -1;                                   // -dp (default: from W; resumed: from the work file)
-    uint64_t kn = 0;                               // -kn: kangaroos per engine (default: from W; resumed: from the work file)
-    uint64_t seed = 0;
-    bool seed_given = false;
-    int wt = 180;                                  // -wt: seconds between two saves of kangaroo.work
-    uint64_t ksteps = 0;                           // -ksteps: stop (saved, rc 3) once this many steps were walked in total
-    bool cpuseed = false;                          // -kcpuseed: start points from the host's comb instead of bsgs_kangaroo_seed
-    bool sym = false;                              // -ksym: the symmetric walk (negation map)
-    uint32_t jumps = 0;                            // -kjumps: jump points of the symmetric walk (default 1024; resumed: from the work file)
-    double jumpscale = 0.0;                        // -kjumpscale: mean jump = scale * N_k sqrt(W) / 4 (default KSYM_JUMPSCALE; resumed: from the work file)
-};
 const double KSYM_JUMPSCALE = 2.0;                 // DESIGN.md 10, "jump scale": the best of the measured sweep
+}  // namespace
 
-KangConfig parse_kangaroo_args(int argc, char **argv)
+KangConfig kang::parse_kangaroo_args(int argc, char **argv)
 {
     KangConfig c;
     for (int i = 1; i < argc; i++) {
@@ -488,7 +502,8 @@ KangConfig parse_kangaroo_args(int argc, char **argv)
         auto next = [&]() -> std::string { if (i + 1 >= argc) die("missing value for " + a); return argv[++i]; };
         if (a == "-kangaroo") continue;
         else if (a == "-h") { usage(Config()); exit(0); }
-        else if (a == "-pb") c.pub = cut_hex(next());
+        else if (a == "-pb") { c.pub = cut_hex(next()); c.pub_given = true; }
+        else if (a == "-infile") c.infile = next();
         else if (a == "-pk") c.pk = cut_hex(next());
         else if (a == "-pke") c.pke = cut_hex(next());
         else if (a == "-d") c.devices = next();
@@ -503,12 +518,33 @@ KangConfig parse_kangaroo_args(int argc, char **argv)
         else if (a == "-ksym") c.sym = true;
         else if (a == "-kjumps") { c.jumps = (uint32_t)strtoul(next().c_str(), nullptr, 10); if (c.jumps < 64 || c.jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (c.jumps & (c.jumps - 1))) die("-kjumps must be a power of two, 64..4096"); }
         else if (a == "-kjumpscale") { c.jumpscale = atof(next().c_str()); if (!(c.jumpscale >= 1.0 / 64 && c.jumpscale <= 64.0)) die("-kjumpscale must be 1/64..64"); }
-        else if (a == "-w" || a == "-htsz" || a == "-infile" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table, one public key)");
+        else if (a == "-w" || a == "-htsz" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table)");
         else die("Unknown parameter with -kangaroo: " + a);
     }
     if (!c.sym && (c.jumps || c.jumpscale != 0.0)) die("-kjumps and -kjumpscale belong to -ksym");
+    if (!c.infile.empty()) {
+        if (c.pub_given) die("-kangaroo: -pb and -infile exclude each other (the keys come from the file)");
+        if (c.sym) die("-kangaroo -ksym cannot be combined with -infile: the symmetric walk keeps its last jump index in the flag bits that carry the key of a wild kangaroo, and its collision rule across keys is not built");
+    }
     return c;
 }
+
+Plan kang::plan_herd(double sqrtW, uint32_t engines, int cus, int dp_arg, uint64_t kn_arg)
+{
+    Plan pl;
+    pl.engines = engines;
+    pl.dp = dp_arg >= 0 ? (uint32_t)dp_arg : (uint32_t)std::min(32.0, std::max(0.0, std::ceil(std::log2(2.0 * sqrtW / 33554432.0))));
+    const uint64_t full = (uint64_t)cus * 1024 * 16;
+    uint64_t kn = kn_arg ? kn_arg : (uint64_t)std::min((double)full, sqrtW / 8.0 / std::ldexp(1.0, (int)pl.dp) / pl.engines);
+    kn = std::max<uint64_t>(kn, 64);
+    pl.G = 16;                                                        // fewer kangaroos per thread only while the GPU would have less than two waves per SIMD
+    while (pl.G > 1 && kn / pl.G < (uint64_t)cus * 512) pl.G /= 2;
+    pl.kn = std::max<uint64_t>(64ull * pl.G, kn / (64ull * pl.G) * (64ull * pl.G));
+    pl.S = pl.cap = 0; pl.expected = 0.0;
+    return pl;
+}
+
+namespace {
 
 // what the engines, the collector and the saver share
 struct Shared {
@@ -531,7 +567,6 @@ struct Shared {
     std::vector<std::vector<bsgs_kangaroo_state>> saved;      // per engine: the herd as downloaded at the last park or at the end
 };
 
-struct Plan { uint32_t engines, dp, G, S, cap; uint64_t kn; double expected; };
 volatile sig_atomic_t signalled = 0;
 void on_signal(int) { signalled = 1; }
 }  // namespace
@@ -540,6 +575,7 @@ int kangaroo_main(int argc, char **argv)
 {
     printf("BSGS MI355X kangaroo mode on %s\n", bsgs_version());
     const KangConfig c = parse_kangaroo_args(argc, argv);
+    if (!c.infile.empty()) return kangaroo_multi_main(c);
     Affine P;
     if (!hs::parse_pubkey(P, c.pub) || !hs::on_curve(P)) die("Invalid Public Key (-pb) length!!!");
     Scalar lo, hi;
@@ -593,15 +629,8 @@ int kangaroo_main(int argc, char **argv)
     { bsgs_dev *d = nullptr; CK(bsgs_dev_open(gpus[0], &d)); bsgs_dev_cu_count(d, &cus); bsgs_dev_close(d); }
     // defaults from W: expected DPs (2 sqrt(W) / 2^dp) within 2^25 host entries, DP overhead N_k 2^dp at most sqrt(W) / 8, a full herd is 16 kangaroos
     // per thread at four waves per SIMD (one batch inversion per block costs about 70 multiplications per thread: 16 kangaroos share it)
-    Plan pl;
-    pl.engines = (uint32_t)gpus.size();
-    pl.dp = resume ? wf.h.dp : c.dp >= 0 ? (uint32_t)c.dp : (uint32_t)std::min(32.0, std::max(0.0, std::ceil(std::log2(2.0 * sqrtW / 33554432.0))));
-    const uint64_t full = (uint64_t)cus * 1024 * 16;
-    uint64_t kn = c.kn ? c.kn : (uint64_t)std::min((double)full, sqrtW / 8.0 / std::ldexp(1.0, (int)pl.dp) / pl.engines);
-    kn = std::max<uint64_t>(kn, 64);
-    pl.G = 16;                                                        // fewer kangaroos per thread only while the GPU would have less than two waves per SIMD
-    while (pl.G > 1 && kn / pl.G < (uint64_t)cus * 512) pl.G /= 2;
-    kn = std::max<uint64_t>(64ull * pl.G, kn / (64ull * pl.G) * (64ull * pl.G));
+    Plan pl = plan_herd(sqrtW, (uint32_t)gpus.size(), cus, resume ? (int)wf.h.dp : c.dp, c.kn);
+    uint64_t kn = pl.kn;
     if (resume) { kn = wf.h.herd; pl.G = wf.h.per_thread; }          // the plan of the run that saved, not this GPU's
     if (kn > (1ull << 26)) die("-kn: at most 2^26 kangaroos per engine");
     pl.kn = kn;

@@ -1,0 +1,99 @@
+// host_kangaroo.h -- what the two kangaroo hosts share (host_kangaroo.cpp: one public key; host_kangaroo_multi.cpp: a list of keys in one range): the seeded
+// stream and the herd offsets, the host's comb, the command line and the plan of a run from the range width.
+#pragma once
+#include "host.h"
+
+namespace kang {
+using Clock = std::chrono::steady_clock;
+typedef unsigned __int128 u128;
+typedef __int128 i128;
+inline double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+inline uint64_t splitmix64(uint64_t &state)
+{
+    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+inline u128 draw128(uint64_t &state) { const uint64_t lo = splitmix64(state), hi = splitmix64(state); return ((u128)hi << 64) | lo; }
+// start offsets (tests/kangaroo_model.py herd_offset): tame t uniform in [1, W), wild u uniform in [-W/2, W/2), both from the seeded stream
+inline i128 herd_offset(uint64_t &state, u128 W, bool wild)
+{
+    const u128 r = draw128(state);
+    return wild ? (i128)(r % W) - (i128)(W / 2) : (i128)(1 + r % (W - 1));
+}
+inline Scalar sc_from_i128(i128 v) { return v >= 0 ? hs::sc_from_u128((u128)v) : hs::sc_neg(hs::sc_from_u128((u128)-v)); }
+
+// fixed-base comb for 128-bit scalars: table[k][v] = v * 2^(8k) * G, sixteen mixed additions per point
+struct Comb {
+    std::vector<std::vector<Affine>> tab;
+    Comb()
+    {
+        Affine base = hs::G;
+        for (int k = 0; k < 16; k++) {
+            std::vector<Affine> m = hs::multiples(base, 256);              // base, 2 base, ..., 256 base
+            tab.push_back(std::vector<Affine>(m.begin(), m.end() - 1));
+            base = m.back();
+        }
+    }
+    hs::Jac mul(u128 s) const
+    {
+        hs::Jac r; r.inf = true;
+        for (int k = 0; k < 16; k++) { const unsigned v = (unsigned)(s >> (8 * k)) & 255u; if (v) r = hs::jac_add_affine(r, tab[k][v - 1]); }
+        return r;
+    }
+};
+
+
+struct KangConfig {
+    std::string devices, pub = Config().pub, pk = Config().pk, pke = Config().pke, dir = ".", wl;
+    int dp = -1;                                   // -dp (default: from W; resumed: from the work file)
+    uint64_t kn = 0;                               // -kn: kangaroos per engine (default: from W; resumed: from the work file)
+    uint64_t seed = 0;
+    bool seed_given = false;
+    int wt = 180;                                  // -wt: seconds between two saves of kangaroo.work
+    uint64_t ksteps = 0;                           // -ksteps: stop (saved, rc 3) once this many steps were walked in total
+    bool cpuseed = false;                          // -kcpuseed: start points from the host's comb instead of bsgs_kangaroo_seed
+    std::string infile;                            // -infile: a list of public keys in the one range (host_kangaroo_multi.cpp)
+    bool pub_given = false;
+    bool sym = false;                              // -ksym: the symmetric walk (negation map)
+    uint32_t jumps = 0;                            // -kjumps: jump points of the symmetric walk (default 1024; resumed: from the work file)
+    double jumpscale = 0.0;                        // -kjumpscale: mean jump = scale * N_k sqrt(W) / 4 (default KSYM_JUMPSCALE; resumed: from the work file)
+};
+KangConfig parse_kangaroo_args(int argc, char **argv);
+
+struct Plan { uint32_t engines, dp, G, S, cap; uint64_t kn; double expected; };
+// defaults from W: expected DPs (2 sqrt(W) / 2^dp) within 2^25 host entries, DP overhead N_k 2^dp at most sqrt(W) / 8, a full herd is 16 kangaroos per
+// thread at four waves per SIMD; dp_arg < 0 / kn_arg == 0: chosen here.  S and cap are left to the caller (they depend on the expected total).
+Plan plan_herd(double sqrtW, uint32_t engines, int cus, int dp_arg, uint64_t kn_arg);
+
+// ---- the work file <dir>/kangaroo.work: version 1 the plain walk, 2 -ksym, 3 a list of keys (-infile) ------------------------------
+const uint32_t WORK_VERSION = 1, WORK_VERSION_SYM = 2, WORK_VERSION_KEYS = 3;       // 2: written and read by -ksym only; the header continues behind the fingerprint
+struct WorkHeader {
+    uint32_t version = WORK_VERSION, jumps = 0;
+    double jumpscale = 0.0;
+    uint64_t cycles = 0;
+    uint32_t engines = 0, dp = 0, per_thread = 0;
+    uint64_t herd = 0, seed = 0, rng = 0, steps = 0, dps = 0, dropped = 0, false_matches = 0, reseeds = 0, table = 0;
+    double elapsed = 0.0;
+    std::string fingerprint;                       // 40 hex digits
+};
+struct WorkLink { uint32_t j, k; i128 delta; };                  // k_j = k_k + delta
+// version 3, between header and table: per key a status byte (1 solved) and the key when solved, the link counters, the open links
+struct WorkKeys { std::vector<uint8_t> solved; std::vector<Scalar> key; std::vector<WorkLink> links; uint64_t kept = 0, resolved = 0; };
+struct WorkFile {
+    WorkHeader h;
+    WorkKeys keys;
+    std::vector<uint8_t> table;                    // 32 bytes per entry
+    std::vector<std::vector<uint8_t>> herds;       // per engine: herd * 96 bytes (bsgs_kangaroo_state)
+    std::vector<std::vector<uint32_t>> reseed;     // per engine: kangaroos waiting for a new start
+};
+bool write_work_file(const std::string &dst, const std::string &tmp, const WorkHeader &h, const std::vector<uint8_t> &table,
+                     const std::vector<const std::vector<bsgs_kangaroo_state> *> &herds, const std::vector<std::vector<uint32_t>> &reseed, const WorkKeys *keys = nullptr);
+// "" when the file is a complete work file of version `want` (0: of any version), else what is wrong with it
+std::string read_work_file(const std::string &path, WorkFile &w, bool with_body, uint32_t want);
+std::string keys_fingerprint(const std::vector<Affine> &P, const Scalar &lo, const Scalar &hi, const WorkHeader &h);
+}  // namespace kang
+
+int kangaroo_multi_main(const kang::KangConfig &c);      // host_kangaroo_multi.cpp: -kangaroo -infile

@@ -143,6 +143,10 @@ int selftest(int argc, char **argv)
             return kangaroo_sym_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-sym-roundtrip") {
             return kangaroo_sym_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-multi-roundtrip") {                    // the same through a version-3 work file in the middle of the stream
+            return kangaroo_multi_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-multi") {                              // the table for a list of keys on a scripted record stream (host_kangaroo_multi.cpp)
+            return kangaroo_multi_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo") {                                    // the rest of the command line: range, public key, record stream (host_kangaroo.cpp)
             return kangaroo_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "joblist" && i + 1 < a.size()) {                  // the rest of the command line is the script

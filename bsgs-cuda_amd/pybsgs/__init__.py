@@ -28,6 +28,7 @@ NATIVE_SYMBOLS = [
     "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
     "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym",
+    "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc"]
@@ -67,6 +68,7 @@ class KangarooRecord(C.Structure):
 
 KANGAROO_JUMPS, KANGAROO_WILD, KANGAROO_DEAD = 64, 1, 0x80000000
 KANGAROO_NEG, KANGAROO_CYCLE = 2, 4                # the symmetric walk (kangaroo_setup_sym)
+KANGAROO_KEY_SHIFT, KANGAROO_MAX_KEYS = 8, 65535   # many keys in one herd (kangaroo_set_keys): a wild kangaroo's key index, 16 bits of its flags
 
 _lib = None
 
@@ -175,6 +177,8 @@ def lib():
             "bsgs_kangaroo_download": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
             "bsgs_kangaroo_run": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
             "bsgs_kangaroo_geometry": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+            "bsgs_kangaroo_set_keys": [vp, u8p, C.c_uint32],
+            "bsgs_kangaroo_seed_keys": [vp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
             "bsgs_kangaroo_seed": [vp, u8p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         }
         for name, args in sig.items():
@@ -673,6 +677,21 @@ class Device:
         ninf, first_inf = C.c_uint32(), C.c_uint32()
         _chk(self.L.bsgs_kangaroo_seed(self.h, q, (C.c_uint32 * n)(*idx) if idx is not None else None, first, n, d, (C.c_uint32 * n)(*flags), C.byref(ninf),
                                        C.byref(first_inf)))
+        return ninf.value, first_inf.value
+
+    def kangaroo_set_keys(self, Qs):
+        """the key list of the herd: affine points Q_k = (x, y), 1..KANGAROO_MAX_KEYS of them; replaces an earlier list"""
+        _chk(self.L.bsgs_kangaroo_set_keys(self.h, b"".join(le32(x) + le32(y) for x, y in Qs), len(Qs)))
+
+    def kangaroo_seed_keys(self, offsets, flags, keys, first=0, idx=None):
+        """as kangaroo_seed with one Q per position: a wild position k starts at Q_keys[k] + d*G with flags KANGAROO_WILD | keys[k] << KANGAROO_KEY_SHIFT; a
+        tame one has keys[k] == 0.  -> (starts at infinity, lowest position of one)"""
+        n = len(offsets)
+        assert len(flags) == n and len(keys) == n and (idx is None or len(idx) == n)
+        d = b"".join((v % (1 << 128)).to_bytes(16, "little") for v in offsets)
+        ninf, first_inf = C.c_uint32(), C.c_uint32()
+        _chk(self.L.bsgs_kangaroo_seed_keys(self.h, (C.c_uint32 * n)(*idx) if idx is not None else None, first, n, d, (C.c_uint32 * n)(*flags),
+                                            (C.c_uint32 * n)(*keys), C.byref(ninf), C.byref(first_inf)))
         return ninf.value, first_inf.value
 
     def kangaroo_geometry(self):
