@@ -247,6 +247,45 @@ extern "C" int bsgs_selftest_fe(bsgs_dev *d, int op, const uint8_t *a, const uin
     return BSGS_OK;
 }
 
+// three operands and the raw representation (fe3_selftest_kernel: op 0..12), or fe_inv_block alone on a (inv_block_selftest_kernel: op 16..20, b and c unused,
+// n a multiple of the block size)
+extern "C" int bsgs_selftest_fe3(bsgs_dev *d, int op, int raw, const uint8_t *a, const uint8_t *b, const uint8_t *c, uint8_t *out, uint32_t n)
+{
+    if (!d || !a || !out || !n) return fail(BSGS_ERR_ARG, "null");
+    const bool block = op >= BSGS_FE3_INV_BLOCK_KANG && op <= BSGS_FE3_INV_BLOCK2_TILE_PAIR128;
+    if (!block && (op < 0 || op >= FE3_OP_COUNT)) return fail(BSGS_ERR_ARG, "selftest_fe3: no op %d", op);
+    if (!block && (!b || !c)) return fail(BSGS_ERR_ARG, "null");
+    const uint32_t W = op >= BSGS_FE3_INV_BLOCK2_TILE ? 2u : 4u;
+    if (block && n % (64u * W)) return fail(BSGS_ERR_ARG, "selftest_fe3: %u elements, not a multiple of the block size %u", n, 64u * W);
+    HIPCHK(hipSetDevice(d->id));
+    const size_t bytes = (size_t)n * 32;
+    fe *buf = nullptr;                                         // a | b | c | out
+    HIPCHK(hipMalloc(&buf, 4 * bytes));
+    fe *da = buf, *db = buf + n, *dc = buf + 2 * (size_t)n, *dout = buf + 3 * (size_t)n;
+    hipError_t e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !block) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !block) e = hipMemcpy(dc, c, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid(n / (64u * W)), bs(64u * W);
+        switch (op) {
+        case BSGS_FE3_INV_BLOCK_KANG: hipLaunchKernelGGL((inv_block_selftest_kernel<KANG_REGION, 4>), grid, bs, 4u * KANG_REGION, d->stream, raw, da, dout); break;
+        case BSGS_FE3_INV_BLOCK_SEED: hipLaunchKernelGGL((inv_block_selftest_kernel<SEED_REGION, 4>), grid, bs, 4u * SEED_REGION, d->stream, raw, da, dout); break;
+        case BSGS_FE3_INV_BLOCK_TILE: hipLaunchKernelGGL((inv_block_selftest_kernel<INVB_TILE_REGION, 4>), grid, bs, 4u * INVB_TILE_REGION, d->stream, raw, da, dout); break;
+        case BSGS_FE3_INV_BLOCK2_TILE: hipLaunchKernelGGL((inv_block_selftest_kernel<INVB_TILE_REGION, 2>), grid, bs, 2u * INVB_TILE_REGION, d->stream, raw, da, dout); break;
+        case BSGS_FE3_INV_BLOCK2_TILE_PAIR128:
+            hipLaunchKernelGGL((inv_block_selftest_kernel<INVB_TILE_REGION_PAIR128, 2>), grid, bs, 2u * INVB_TILE_REGION_PAIR128, d->stream, raw, da, dout);
+            break;
+        default: hipLaunchKernelGGL(fe3_selftest_kernel, dim3((n + 63) / 64), dim3(64), 0, d->stream, op, raw, da, db, dc, dout, n); break;
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(BSGS_ERR_HIP, "selftest_fe3: %s", hipGetErrorString(e));
+    return BSGS_OK;
+}
+
 // the low-64-bit squaring path against the full-width one on n*iters pseudo-random cases: counts[0] mismatches (must be 0),
 // counts[1] cases that took the exact path, counts[2] cases
 extern "C" int bsgs_selftest_lo64(bsgs_dev *d, const uint8_t *a, const uint8_t *b, uint32_t n, uint32_t iters, uint64_t counts[3])

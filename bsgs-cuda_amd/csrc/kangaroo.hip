@@ -8,7 +8,6 @@
 #include "bsgs_internal.h"
 
 #define KANG_NJ 64u
-#define KANG_REGION 6144u                                   // LDS bytes per wave for fe_inv_block<REGION, 4> (its leader uses offsets 0, 2048 and 4096)
 #define KANG_TABLE_OFF (4u * KANG_REGION)                   // the jump table behind the inversion regions: x[64] | y[64] | s[64] (4608 bytes)
 #define KANG_TABLE_BYTES (KANG_NJ * 32u * 2u + KANG_NJ * 8u)
 #define KANG_LDS (KANG_TABLE_OFF + KANG_TABLE_BYTES)
@@ -23,10 +22,6 @@ struct KangArgs {
     u32 N, T, G, steps, dp_mask, cap;
 };
 
-__device__ __forceinline__ bool fe_is_zero(const fe &a)
-{
-    return (a.v[0] | a.v[1] | a.v[2] | a.v[3] | a.v[4] | a.v[5] | a.v[6] | a.v[7]) == 0u;
-}
 __device__ __forceinline__ void lds_fe(fe &r, const char *q)
 {
     const u32x4 lo = *(const u32x4 *)q, hi = *(const u32x4 *)(q + 16);

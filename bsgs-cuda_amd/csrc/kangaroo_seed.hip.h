@@ -7,7 +7,6 @@
 
 #include <algorithm>
 
-#define SEED_REGION 6144u                                   // LDS bytes per wave for fe_inv_block<REGION, 4>
 #define SEED_LDS (4u * SEED_REGION)
 #define SEED_WINDOWS 16u
 #define SEED_CHUNK (1u << 20)                               // positions per launch: bounds the staging (52 bytes per position)

@@ -28,7 +28,7 @@ NATIVE_SYMBOLS = [
     "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
     "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym",
-    "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys",
+    "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_selftest_fe3",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc"]
@@ -65,6 +65,12 @@ class KangarooState(C.Structure):
 class KangarooRecord(C.Structure):
     _fields_ = [("x", C.c_uint8 * 32), ("d", C.c_uint8 * 16), ("kangaroo", C.c_uint32), ("flags", C.c_uint32), ("step", C.c_uint32), ("reserved", C.c_uint32)]
 
+
+# bsgs_selftest_fe3: ops of the three-operand field selftest, and fe_inv_block alone (four waves per block: the strides of the kangaroo, seed and tile kernels;
+# two waves: the tile kernels' two strides)
+FE3_SQR_ADD2, FE3_NEG, FE3_CANON, FE3_ADD, FE3_SUB, FE3_MUL, FE3_SQR, FE3_INV = range(8)
+FE3_IS_P, FE3_IS_ZERO, FE3_EQ, FE3_ADD_IS_P, FE3_SUB_IS_ZERO = range(8, 13)
+FE3_INV_BLOCK_KANG, FE3_INV_BLOCK_SEED, FE3_INV_BLOCK_TILE, FE3_INV_BLOCK2_TILE, FE3_INV_BLOCK2_TILE_PAIR128 = range(16, 21)
 
 KANGAROO_JUMPS, KANGAROO_WILD, KANGAROO_DEAD = 64, 1, 0x80000000
 KANGAROO_NEG, KANGAROO_CYCLE = 2, 4                # the symmetric walk (kangaroo_setup_sym)
@@ -125,6 +131,7 @@ def lib():
             "bsgs_dev_stream": [vp, C.POINTER(vp)],
             "bsgs_steps_per_tile": [vp, C.POINTER(C.c_uint64)],
             "bsgs_selftest_fe": [vp, C.c_int, u8p, u8p, vp, C.c_uint32],
+            "bsgs_selftest_fe3": [vp, C.c_int, C.c_int, u8p, u8p, u8p, vp, C.c_uint32],
             "bsgs_selftest_xs": [vp, u8p, u8p, C.c_uint64, C.c_uint32, vp],
             "bsgs_bench_random_read": [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)],
             "bsgs_bench_modmul": [vp, C.POINTER(C.c_double)],
@@ -540,6 +547,14 @@ class Device:
         b = b"".join(le32(v) for v in b_list)
         out = C.create_string_buffer(32 * n)
         _chk(self.L.bsgs_selftest_fe(self.h, op, a, b, C.cast(out, C.c_void_p), n))
+        return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(n)]
+
+    def selftest_fe3(self, op, a_list, b_list=None, c_list=None, raw=False):
+        """op (FE3_*) on every (a, b, c), any values below 2^256; raw: the result as the device function left it, not canonicalised.  The predicates give 0 or 1."""
+        n = len(a_list)
+        a, b, c = (b"".join(le32(v) for v in (lst if lst is not None else a_list)) for lst in (a_list, b_list, c_list))
+        out = C.create_string_buffer(32 * n)
+        _chk(self.L.bsgs_selftest_fe3(self.h, op, 1 if raw else 0, a, b, c, C.cast(out, C.c_void_p), n))
         return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(n)]
 
     def selftest_lo64(self, a_list, b_list, iters):
