@@ -1,7 +1,9 @@
 // host.h -- declarations shared by the translation units of bsgs_mi355x, the C++ host of the MI355X BSGS solver (see bsgs_host.cpp for the reference
 // file:line map).  host_config.cpp: command line, limits, checkpoint; host_files.cpp: table files and the CPU-only generator; host_resolver.cpp: dispenser and hit
 // resolver; host_jobs.cpp: Job, the key list and its lanes (JobList); host_tune.cpp: Tune; host_engines.cpp: per-GPU engines (load, verify, search thread);
-// host_selftest.cpp: -selftest; host_kangaroo.cpp: -kangaroo; host_kangaroo_multi.cpp: -kangaroo -infile and its table for a list of keys; bsgs_host.cpp: main and the start-up steps.
+// host_selftest.cpp: -selftest; bsgs_host.cpp: main and the start-up steps.  -kangaroo: host_kangaroo_run.cpp: the prologue and the run loop of every mode (engines, collector, saving, signals)
+// behind the seam of host_kangaroo_run.h; host_kangaroo.cpp: command line, one key (plain and -ksym) and its table; host_kangaroo_multi.cpp: -infile and its table for a list of keys;
+// host_kangaroo_work.cpp: the work file kangaroo.work.
 #pragma once
 #include "../../include/bsgs_hip.h"
 #include "../csrc/host_secp.h"
@@ -224,8 +226,8 @@ void gpu_thread(Job *J, int gpu, int slot, bsgs_dev *dev);
 int selftest(int argc, char **argv);
 // the lines a found key is reported with (1_9_7File.pb:5146-5160): returns the win.txt text, `console` receives the console block
 std::string key_lines(int listpos, const Scalar &key, const Affine &pub, std::string &console);
-// host_kangaroo.cpp: bsgs_mi355x -kangaroo, -selftest kangaroo (the table of distinguished points on a scripted record stream), and the work file's
-// selftests kangaroo-work / kangaroo-table-roundtrip
+// host_kangaroo.cpp: bsgs_mi355x -kangaroo, -selftest kangaroo (the table of distinguished points on a scripted record stream) and kangaroo-table-roundtrip;
+// host_kangaroo_work.cpp: -selftest kangaroo-work
 int kangaroo_main(int argc, char **argv);
 int kangaroo_selftest(const std::vector<std::string> &args);
 int kangaroo_work_selftest(const std::vector<std::string> &args);

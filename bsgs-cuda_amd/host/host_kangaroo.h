@@ -1,5 +1,6 @@
-// host_kangaroo.h -- what the two kangaroo hosts share (host_kangaroo.cpp: one public key; host_kangaroo_multi.cpp: a list of keys in one range): the seeded
-// stream and the herd offsets, the host's comb, the command line and the plan of a run from the range width.
+// host_kangaroo.h -- what the kangaroo hosts share (host_kangaroo.cpp: one public key, plain and -ksym; host_kangaroo_multi.cpp: a list of keys in one range;
+// host_kangaroo_run.{h,cpp}: the prologue and the run loop both go through; host_kangaroo_work.cpp: the work file): the seeded stream and the herd offsets,
+// the host's comb and its start points, the command line, the plan of a run from the range width, the work file's reader and writer, the selftests' helpers.
 #pragma once
 #include "host.h"
 
@@ -44,7 +45,9 @@ struct Comb {
         return r;
     }
 };
-
+// start points from the comb: state k is d[k] * G, plus *Q[k] where Q[k] is not null, with flags fl[k]; returns the positions that stand at infinity (x and y
+// zero there; what such a start means is the caller's: the key itself for one key, a dead kangaroo and a solved key for a list)
+std::vector<size_t> comb_states(const Comb &C, const std::vector<i128> &d, const std::vector<uint32_t> &fl, const std::vector<const Affine *> &Q, std::vector<bsgs_kangaroo_state> &out);
 
 struct KangConfig {
     std::string devices, pub = Config().pub, pk = Config().pk, pke = Config().pke, dir = ".", wl;
@@ -89,11 +92,22 @@ struct WorkFile {
     std::vector<std::vector<uint8_t>> herds;       // per engine: herd * 96 bytes (bsgs_kangaroo_state)
     std::vector<std::vector<uint32_t>> reseed;     // per engine: kangaroos waiting for a new start
 };
-bool write_work_file(const std::string &dst, const std::string &tmp, const WorkHeader &h, const std::vector<uint8_t> &table,
-                     const std::vector<const std::vector<bsgs_kangaroo_state> *> &herds, const std::vector<std::vector<uint32_t>> &reseed, const WorkKeys *keys = nullptr);
-// "" when the file is a complete work file of version `want` (0: of any version), else what is wrong with it
-std::string read_work_file(const std::string &path, WorkFile &w, bool with_body, uint32_t want);
+// host_kangaroo_work.cpp.  write_work: under `tmp`, then renamed; herds by pointer: they are the large part
+bool write_work(const std::string &dst, const std::string &tmp, const WorkHeader &h, const std::vector<uint8_t> &table,
+                const std::vector<const std::vector<bsgs_kangaroo_state> *> &herds, const std::vector<std::vector<uint32_t>> &reseed, const WorkKeys *keys = nullptr);
+// "" when the file is a complete work file of version `want` (0: of any version), else what is wrong with it; with_body = false reads the header and checks
+// the sections' sizes only
+std::string read_work(const std::string &path, WorkFile &w, bool with_body, uint32_t want);
+// SHA-1 over what a resumed run must share with the run that saved: one key (versions 1 and 2), a list (version 3)
+std::string kangaroo_fingerprint(const Affine &P, const Scalar &lo, const Scalar &hi, const WorkHeader &h);
 std::string keys_fingerprint(const std::vector<Affine> &P, const Scalar &lo, const Scalar &hi, const WorkHeader &h);
+
+// what the -selftest kangaroo* items share: the range (width below 2^128) and the comma-separated public keys of a command line, the work file a round trip
+// goes through (a temporary one, or BSGS_SELFTEST_WORK to write and keep; "" when none can be made), a scripted record split at its commas
+bool parse_pubs(const std::string &csv, std::vector<Affine> &pubs);
+bool parse_range_pubs(const std::string &pk, const std::string &pke, const std::string &csv, Scalar &lo, Scalar &hi, u128 &W, std::vector<Affine> &pubs);
+std::string selftest_work_path(bool &keep);
+std::vector<std::string> split_commas(const std::string &rec);
 }  // namespace kang
 
 int kangaroo_multi_main(const kang::KangConfig &c);      // host_kangaroo_multi.cpp: -kangaroo -infile

@@ -1,13 +1,11 @@
 // host_kangaroo_multi.cpp -- the table of distinguished points for a LIST of public keys in one range (include/bsgs_hip.h "Kangaroo, many keys" states the
 // rule; tests/kangaroo_multi_model.py MultiTable restates it): an owner per entry, links between two unsolved keys, a solved key's entries acting as tame
-// ones, -selftest kangaroo-multi / kangaroo-multi-roundtrip, which drive the table with a scripted record stream and no GPU, and the run itself:
-// bsgs_mi355x -kangaroo -infile, saved to kangaroo.work version 3 and continued with -wl.
+// ones, -selftest kangaroo-multi / kangaroo-multi-roundtrip, which drive the table with a scripted record stream and no GPU, and ListMode, what
+// bsgs_mi355x -kangaroo -infile puts behind the driver's seam (host_kangaroo_run.h): saved to kangaroo.work version 3 and continued with -wl.
 #include "host_kangaroo_multi.h"
-#include "host_kangaroo.h"
+#include "host_kangaroo_run.h"
 
-#include <csignal>
 #include <map>
-#include <random>
 
 namespace {
 typedef unsigned __int128 u128;
@@ -146,10 +144,7 @@ bool MultiKeyTable::restore(const uint8_t *entries, uint64_t n, uint64_t false_m
 // one scripted record into the table, its event lines printed; false: the record does not parse
 static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::string &rec)
 {
-    std::vector<std::string> f;
-    std::stringstream ss(rec);
-    std::string tok;
-    while (std::getline(ss, tok, ',')) f.push_back(tok);
+    const std::vector<std::string> f = kang::split_commas(rec);
     if (f.size() != 4 || f[0].empty() || !strchr("TWD", f[0][0]) || (f[0][0] != 'W' && f[0].size() != 1)) return false;
     uint32_t flags = f[0][0] == 'D' ? BSGS_KANGAROO_DEAD : 0u;
     if (f[0][0] == 'W') {
@@ -174,6 +169,18 @@ static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::
     }
     return true;
 }
+// the keys equal to pk*G are solved up front: "presolved <k>"
+static void presolve_scripted(MultiKeyTable &tab, const std::vector<Affine> &pubs, const Scalar &lo)
+{
+    const Affine aG = hs::point_mul(hs::G, lo);
+    for (size_t k = 0; k < pubs.size(); k++)
+        if (hs::fe_equal(pubs[k].x, aG.x) && hs::fe_equal(pubs[k].y, aG.y)) { tab.presolve((uint32_t)k, lo); printf("presolved %zu\n", k); }
+}
+static void print_summary(const MultiKeyTable &tab)
+{
+    printf("summary %zu %llu %llu %llu %llu %u\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds(),
+           (unsigned long long)tab.links_kept(), (unsigned long long)tab.links_resolved(), tab.solved());
+}
 
 // -selftest kangaroo-multi <pk hex> <pke hex> <pubkey>[,<pubkey>...] <record>...   record = T|W<k>|D,<x hex>,<d hex: 128-bit two's complement>,<kangaroo>
 // (W<k>: a wild kangaroo of the key at list position k, from 0; D: a dead record).  A key equal to pk*G is solved up front: "presolved <k>".  One line per
@@ -182,29 +189,13 @@ static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::
 int kangaroo_multi_selftest(const std::vector<std::string> &a)
 {
     if (a.size() < 3) return 2;
-    Scalar lo, hi;
-    if (!hs::fe_from_hex(lo, a[0]) || !hs::fe_from_hex(hi, a[1])) return 2;
-    const Scalar w = hs::sc_sub(hi, lo);
-    if (w.l[2] || w.l[3]) return 2;
-    const u128 W = (((u128)w.l[1] << 64) | w.l[0]) + 1;
+    Scalar lo, hi; u128 W;
     std::vector<Affine> pubs;
-    {
-        std::stringstream ss(a[2]);
-        std::string tok;
-        while (std::getline(ss, tok, ',')) {
-            Affine P;
-            if (!hs::parse_pubkey(P, cut_hex(tok)) || !hs::on_curve(P)) return 2;
-            pubs.push_back(P);
-        }
-    }
-    if (pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
+    if (!kang::parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
     MultiKeyTable tab(lo, W, pubs);
-    const Affine aG = hs::point_mul(hs::G, lo);
-    for (size_t k = 0; k < pubs.size(); k++)
-        if (hs::fe_equal(pubs[k].x, aG.x) && hs::fe_equal(pubs[k].y, aG.y)) { tab.presolve((uint32_t)k, lo); printf("presolved %zu\n", k); }
+    presolve_scripted(tab, pubs, lo);
     for (size_t i = 3; i < a.size(); i++) if (!multi_scripted_record(tab, pubs.size(), a[i])) return 2;
-    printf("summary %zu %llu %llu %llu %llu %u\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds(),
-           (unsigned long long)tab.links_kept(), (unsigned long long)tab.links_resolved(), tab.solved());
+    print_summary(tab);
     return 0;
 }
 
@@ -214,36 +205,19 @@ int kangaroo_multi_selftest(const std::vector<std::string> &a)
 int kangaroo_multi_roundtrip_selftest(const std::vector<std::string> &a)
 {
     if (a.size() < 4) return 2;
-    Scalar lo, hi;
-    if (!hs::fe_from_hex(lo, a[0]) || !hs::fe_from_hex(hi, a[1])) return 2;
-    const Scalar w = hs::sc_sub(hi, lo);
-    if (w.l[2] || w.l[3]) return 2;
-    const u128 W = (((u128)w.l[1] << 64) | w.l[0]) + 1;
+    Scalar lo, hi; u128 W;
     std::vector<Affine> pubs;
-    {
-        std::stringstream ss(a[2]);
-        std::string tok;
-        while (std::getline(ss, tok, ',')) { Affine P; if (!hs::parse_pubkey(P, cut_hex(tok)) || !hs::on_curve(P)) return 2; pubs.push_back(P); }
-    }
-    if (pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
+    if (!kang::parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
     const size_t split = (size_t)strtoull(a[3].c_str(), nullptr, 10);
     if (split > a.size() - 4) return 2;
-    const char *keep = getenv("BSGS_SELFTEST_WORK");
-    std::string path = keep ? keep : "";
-    if (!keep) {
-        char tmpl[] = "/tmp/kangaroo_work_XXXXXX";
-        const int fd = mkstemp(tmpl);
-        if (fd < 0) return 2;
-        close(fd);
-        path = tmpl;
-    }
-    const Affine aG = hs::point_mul(hs::G, lo);
+    bool keep;
+    const std::string path = kang::selftest_work_path(keep);
+    if (path.empty()) return 2;
     kang::WorkHeader h;
     h.version = kang::WORK_VERSION_KEYS;
     {
         MultiKeyTable first(lo, W, pubs);
-        for (size_t k = 0; k < pubs.size(); k++)
-            if (hs::fe_equal(pubs[k].x, aG.x) && hs::fe_equal(pubs[k].y, aG.y)) { first.presolve((uint32_t)k, lo); printf("presolved %zu\n", k); }
+        presolve_scripted(first, pubs, lo);
         for (size_t i = 0; i < split; i++) if (!multi_scripted_record(first, pubs.size(), a[4 + i])) return 2;
         std::vector<uint8_t> entries;
         kang::WorkKeys wk;
@@ -252,26 +226,23 @@ int kangaroo_multi_roundtrip_selftest(const std::vector<std::string> &a)
         h.table = first.size(); h.false_matches = first.false_matches(); h.reseeds = first.reseeds();
         for (size_t i = 0; i < split; i++) if (a[4 + i][0] != 'D') h.dps++;
         h.fingerprint = kang::keys_fingerprint(pubs, lo, hi, h);
-        if (!kang::write_work_file(path, path + ".temp", h, entries, {}, {}, &wk)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        if (!kang::write_work(path, path + ".temp", h, entries, {}, {}, &wk)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
     }
     kang::WorkFile wf;
-    const std::string bad = kang::read_work_file(path, wf, true, kang::WORK_VERSION_KEYS);
+    const std::string bad = kang::read_work(path, wf, true, kang::WORK_VERSION_KEYS);
     if (!keep) remove(path.c_str());
     if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
     if (kang::keys_fingerprint(pubs, lo, hi, wf.h) != wf.h.fingerprint) { fprintf(stderr, "Recovery file was made with other settings\n"); return 1; }
     MultiKeyTable second(lo, W, pubs);
     if (!second.restore(wf.table.data(), wf.h.table, wf.h.false_matches, wf.h.reseeds, wf.keys)) { fprintf(stderr, "the table section does not load\n"); return 1; }
     for (size_t i = 4 + split; i < a.size(); i++) if (!multi_scripted_record(second, pubs.size(), a[i])) return 2;
-    printf("summary %zu %llu %llu %llu %llu %u\n", second.size(), (unsigned long long)second.false_matches(), (unsigned long long)second.reseeds(),
-           (unsigned long long)second.links_kept(), (unsigned long long)second.links_resolved(), second.solved());
+    print_summary(second);
     return 0;
 }
 
 // ---- bsgs_mi355x -kangaroo -infile FILE: every key of the list in [pk, pke] with ONE herd per engine -----------------------------------------------
 namespace {
 using namespace kang;
-volatile sig_atomic_t multi_signalled = 0;
-void multi_on_signal(int) { multi_signalled = 1; }
 
 // which key a wild kangaroo works on (include/bsgs_hip.h "Kangaroo, many keys", assignment; tests/kangaroo_multi_model.py Assigner)
 class Assigner {
@@ -313,6 +284,205 @@ private:
 };
 }  // namespace
 
+namespace {
+struct ListMode : Mode {
+    ListMode(const KangConfig &c, const std::vector<Affine> &P) : c(c), P(P), L((uint32_t)P.size())
+    {
+        version = WORK_VERSION_KEYS;
+        wl_flag = "-kangaroo -infile -wl"; wl_kind = "a kangaroo.work file of a key list";
+        if (c.cpuseed) herd_label = "herds (host), engine ";
+    }
+    std::string fingerprint(const Prologue &p, const WorkHeader &h) const override { return keys_fingerprint(P, p.lo, p.hi, h); }
+    // a key is known: its KEY[n] block on the console and in win.txt at once, through key_lines as the BSGS path writes it
+    void report(uint32_t k)
+    {
+        std::string console;
+        const std::string win = key_lines((int)k + 1, table->key(k), P[k], console);
+        fputs(console.c_str(), stdout);
+        fflush(stdout);
+        std::ofstream f(c.dir + "/win.txt", std::ios::app | std::ios::binary);
+        f << win;
+        found_n++;
+    }
+    bool before_devices(Prologue &p) override
+    {
+        pro = &p;
+        if (p.resume && p.wf.keys.solved.size() != L) die("Recovery file was made with other settings");
+        if (!p.resume) { Config rc; rc.dir = c.dir; read_recovery(rc); }         // (win.txt starts empty, as on the BSGS path; a resumed run appends to the one it has)
+        p.t0 = Clock::now();
+        table.reset(new MultiKeyTable(p.lo, p.W, P));
+        for (uint32_t k = 0; k < L; k++) same[hs::compress_pubkey(P[k])].push_back(k);
+        // keys solved before any device is opened: P_k == a*G has no affine Q_k; it keeps its slot (G stands in, no kangaroo is assigned)
+        const Affine aG = hs::point_mul(hs::G, p.lo), naG = hs::affine_neg(aG);
+        presolved.assign(L, false);
+        qxy.resize(64 * (size_t)L);
+        Q.resize(L);
+        for (uint32_t k = 0; k < L; k++) {
+            Q[k] = hs::point_add(P[k], naG);
+            if (Q[k].inf) { presolved[k] = true; table->presolve(k, p.lo); if (p.resume) found_n++; else report(k); Q[k] = hs::G; }
+            hs::affine_to_le(Q[k], &qxy[64 * (size_t)k], &qxy[64 * (size_t)k + 32]);
+        }
+        if (p.resume) {                                                            // the file's solved keys are in win.txt already: counted, not written again
+            const uint32_t before = table->solved();
+            if (!table->restore(p.wf.table.data(), p.wf.h.table, p.wf.h.false_matches, p.wf.h.reseeds, p.wf.keys)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
+            std::vector<uint8_t>().swap(p.wf.table);
+            found_n += (int)(table->solved() - before);
+        }
+        open0 = L - table->solved();
+        if (!open0) printf("Found %d of %u\n", found_n, L);
+        return open0 != 0;
+    }
+    // after the prologue: the expectation, the assignment of wild kangaroos to keys (-wl: as the saved states name it), the offsets of the initial herds in
+    // engine order from the seeded stream (the points are computed in each engine's thread, by the GPU or with -kcpuseed by the host's comb)
+    void prepare(Prologue &p, Shared &s)
+    {
+        sh = &s;
+        const Plan &pl = p.pl;
+        const uint64_t kn = pl.kn;
+        half = kn / 2;                                                             // kangaroos [0, half) of an engine are tame, [half, kn) wild
+        overhead = (double)kn * pl.engines * std::ldexp(1.0, (int)pl.dp);
+        exp_lo = 2.0 * std::sqrt((double)open0 * (double)p.W) + overhead; exp_hi = (double)open0 * 2.0 * p.sqrtW + overhead;
+        // (the give-up bound: 20 times L_open 2 sqrt(W) + overhead steps without a new key, L_open the keys open at that moment)
+        printf("Expected steps for %u keys: between 2^%.2f (2 sqrt(L W)) and 2^%.2f (L 2 sqrt(W)), DP overhead included\n", open0, std::log2(exp_lo), std::log2(exp_hi));
+        asg.reset(new Assigner(L, presolved, (kn - half) * pl.engines));
+        if (p.resume) {
+            std::vector<uint32_t> keys((kn - half) * pl.engines);
+            for (uint32_t e = 0; e < pl.engines; e++) for (uint64_t i = half; i < kn; i++) {
+                const uint32_t k = (p.herds[e][i].flags >> BSGS_KANGAROO_KEY_SHIFT) & 0xFFFFu;
+                if (k >= L) die("-kangaroo -wl: a kangaroo of " + p.wl_path + " names key " + std::to_string(k));
+                keys[(uint64_t)e * (kn - half) + (i - half)] = k;
+            }
+            asg->restore(keys, *table);
+            printf("Resumed: %llu steps, %zu DPs, %u of %u keys solved\n", (unsigned long long)p.wf.h.steps, table->size(), table->solved(), L);
+        }
+        if (c.cpuseed) comb.reset(new Comb());
+        steps_mark = s.steps.load();
+        last_solved = table->solved();
+        off0.resize(pl.engines);
+        if (!p.resume) for (uint32_t e = 0; e < pl.engines; e++) { off0[e].resize(kn); for (uint64_t i = 0; i < kn; i++) off0[e][i] = herd_offset(s.rng, p.W, i >= half); }
+    }
+    // under sh->tab_m.  The consequences of FOUND events: the block is written, equal points of the list are solved with it, the key's kangaroos start afresh
+    void on_events(const std::vector<MultiKeyTable::Event> &ev)
+    {
+        const uint64_t wild = pro->pl.kn - half;
+        for (const MultiKeyTable::Event &x : ev) {
+            if (x.what != MultiKeyTable::FOUND) continue;
+            report(x.a);
+            asg->solved(x.a);
+            for (uint64_t w = 0; w < asg->keys().size(); w++) if (asg->keys()[w] == x.a) sh->push_reseed((uint32_t)(w / wild), (uint32_t)(half + w % wild));
+            for (uint32_t o : same[hs::compress_pubkey(P[x.a])]) if (!table->known(o)) {
+                std::vector<MultiKeyTable::Event> more;
+                table->found(o, x.key, more);
+                on_events(more);
+            }
+        }
+        if (table->solved() == L) sh->stop = true;
+    }
+    const char *setup(bsgs_dev *dev) override
+    {
+        const Plan &pl = pro->pl;
+        if (bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup";
+        return bsgs_kangaroo_set_keys(dev, qxy.data(), L) == BSGS_OK ? nullptr : "bsgs_kangaroo_set_keys";
+    }
+    // one seed call: the whole herd (idx empty) or a list; a start at infinity solves its key and the kangaroo is seeded again next round
+    const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &s) override
+    {
+        const uint64_t kn = pro->pl.kn, wild0 = (uint64_t)e * (kn - half);
+        std::vector<uint32_t> use, fl, key;
+        std::vector<i128> d;
+        if (idx.empty()) {
+            fl.resize(kn); key.assign(kn, 0);
+            for (uint64_t i = 0; i < kn; i++) { fl[i] = i >= half ? BSGS_KANGAROO_WILD : 0u; if (i >= half) key[i] = asg->key(wild0 + (i - half)); }
+            d.swap(off0[e]);
+        } else {                                                                   // offsets and keys: under the table's lock and then the stream's
+            std::lock_guard<std::mutex> lt(s.tab_m);
+            std::lock_guard<std::mutex> lk(s.rng_m);
+            for (uint32_t i : idx) {
+                const bool wild = i >= half;
+                uint32_t k = 0;
+                if (wild && !asg->reseed(wild0 + (i - half), *table, &k)) continue;                      // no key is open: the kangaroo rests
+                use.push_back(i); fl.push_back(wild ? BSGS_KANGAROO_WILD : 0u); key.push_back(k);
+                d.push_back(herd_offset(s.rng, pro->W, wild));
+            }
+            if (use.empty()) return nullptr;
+        }
+        uint32_t ninf = 0, first = 0;
+        if (c.cpuseed) {                                                           // the same herd from the host's comb
+            std::vector<uint32_t> word(d.size());
+            std::vector<const Affine *> q(d.size());
+            for (size_t k = 0; k < d.size(); k++) { word[k] = fl[k] | key[k] << BSGS_KANGAROO_KEY_SHIFT; q[k] = fl[k] ? &Q[key[k]] : nullptr; }
+            std::vector<bsgs_kangaroo_state> st;
+            const std::vector<size_t> inf = comb_states(*comb, d, word, q, st);
+            for (size_t k : inf) st[k].flags |= BSGS_KANGAROO_DEAD;
+            if ((use.empty() ? bsgs_kangaroo_upload(dev, 0, (uint32_t)st.size(), st.data()) : bsgs_kangaroo_upload_list(dev, use.data(), (uint32_t)use.size(), st.data())) != BSGS_OK) return "bsgs_kangaroo_upload";
+            if (!inf.empty()) { ninf = 1; first = (uint32_t)inf[0]; }
+        } else if (bsgs_kangaroo_seed_keys(dev, use.empty() ? nullptr : use.data(), 0, (uint32_t)d.size(), (const uint8_t *)d.data(), fl.data(), key.data(), &ninf, &first) != BSGS_OK) return "bsgs_kangaroo_seed_keys";
+        if (ninf) {
+            if (fl[first]) {                                                       // Q_key + u G = infinity: k_key = a - u
+                std::lock_guard<std::mutex> lt(s.tab_m);
+                if (!table->known(key[first])) {
+                    std::vector<MultiKeyTable::Event> ev;
+                    table->found(key[first], hs::sc_add(pro->lo, sc_from_i128(-d[first])), ev);
+                    on_events(ev);
+                }
+            }
+            s.push_reseed(e, use.empty() ? first : use[first]);
+        }
+        return nullptr;
+    }
+    bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &s) override
+    {
+        u128 d;
+        memcpy(&d, r.d, 16);
+        std::vector<MultiKeyTable::Event> ev;
+        table->add(r.x, d, (uint32_t)(e * pro->pl.kn + r.kangaroo), r.flags, ev);
+        for (const MultiKeyTable::Event &x : ev) if (x.what == MultiKeyTable::RESEED) s.push_reseed(e, r.kangaroo);
+        on_events(ev);
+        return true;
+    }
+    bool done() const override { return table->solved() == L; }
+    // give up: 20 times one key's expectation for every key still open, counted from the last key found
+    bool give_up(uint64_t steps) override
+    {
+        const uint32_t solved_now = table->solved();
+        if (solved_now != last_solved) { last_solved = solved_now; steps_mark = steps; }
+        return (double)(steps - steps_mark) > 20.0 * ((double)(L - solved_now) * 2.0 * pro->sqrtW + overhead);
+    }
+    void status(double rate, uint64_t st, uint64_t dps) const override
+    {
+        printf("\r[%u] %.3e steps/s  steps 2^%.2f of expected 2^%.2f..2^%.2f  solved %u/%u  DPs %llu  %.0fs   ", pro->pl.engines, rate, st ? std::log2((double)st) : 0.0,
+               std::log2(exp_lo), std::log2(exp_hi), table->solved(), L, (unsigned long long)dps, since(pro->t0));
+    }
+    const WorkKeys *save(WorkHeader &h, std::vector<uint8_t> &entries) override
+    {
+        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.table = table->size();
+        entries.reserve(32 * table->size());
+        table->write_entries(entries);
+        table->write_keys(wk);
+        return &wk;
+    }
+
+    const KangConfig &c;
+    const std::vector<Affine> &P;
+    const uint32_t L;
+    const Prologue *pro = nullptr;
+    Shared *sh = nullptr;
+    std::unique_ptr<MultiKeyTable> table;
+    std::unique_ptr<Assigner> asg;
+    std::map<std::string, std::vector<uint32_t>> same;                            // list positions that hold the same point
+    std::vector<bool> presolved;
+    std::vector<Affine> Q;
+    std::vector<uint8_t> qxy;
+    std::unique_ptr<Comb> comb;
+    std::vector<std::vector<i128>> off0;
+    WorkKeys wk;
+    int found_n = 0;
+    uint32_t open0 = 0, last_solved = 0;
+    uint64_t half = 0, steps_mark = 0;
+    double overhead = 0.0, exp_lo = 0.0, exp_hi = 0.0;
+};
+}  // namespace
+
 int kangaroo_multi_main(const KangConfig &c)
 {
     Config fc; fc.infile = c.infile;
@@ -322,416 +492,24 @@ int kangaroo_multi_main(const KangConfig &c)
     const uint32_t L = (uint32_t)pub_hex.size();
     std::vector<Affine> P(L);
     for (uint32_t k = 0; k < L; k++) if (!hs::parse_pubkey(P[k], pub_hex[k]) || !hs::on_curve(P[k])) die("Invalid Public Key (-infile, line " + std::to_string(k + 1) + ") length!!!");
-    Scalar lo, hi;
-    if (!hs::fe_from_hex(lo, c.pk) || hs::fe_is_zero(lo)) die("Start range can`t be zero");
-    if (!hs::fe_from_hex(hi, c.pke)) die("Invalid range (-pkend) length!!!");
-    if (hs::fe_cmp(hi, lo) <= 0) die("End range must be more then start range");
-    const Scalar wm1 = hs::sc_sub(hi, lo);
-    if (wm1.l[2] || wm1.l[3] || (wm1.l[1] >> 61)) die("-kangaroo: the range width must be at most 2^125");
-    const u128 W = (((u128)wm1.l[1] << 64) | wm1.l[0]) + 1;
-    if (W < ((u128)1 << 20)) die("-kangaroo: the range width must be at least 2^20");
-    const double Wd = (double)W, sqrtW = std::sqrt(Wd);
-    printf("Kangaroo range [%s, %s], width 2^%.2f, %u public keys\n", hs::fe_to_hex(lo).c_str(), hs::fe_to_hex(hi).c_str(), std::log2(Wd), L);
-    // -wl: the work file is read before any device is looked for; only a version-3 file of this list, range and plan can be continued
-    const bool resume = !c.wl.empty();
-    WorkFile wf;
-    std::string wl_path = c.wl;
-    if (resume) {
-        struct stat sb;
-        if (stat(wl_path.c_str(), &sb) != 0 && stat((c.dir + "/" + c.wl).c_str(), &sb) == 0) wl_path = c.dir + "/" + c.wl;
-        const std::string bad = read_work_file(wl_path, wf, true, WORK_VERSION_KEYS);
-        if (!bad.empty()) die("-kangaroo -infile -wl: " + bad + " (only a kangaroo.work file of a key list can be resumed here; a BSGS recovery file is not supported in kangaroo mode)");
-        std::vector<std::string> dl;
-        { std::stringstream ss(c.devices); std::string tok; while (std::getline(ss, tok, ',')) dl.push_back(tok); }
-        if (keys_fingerprint(P, lo, hi, wf.h) != wf.h.fingerprint || wf.keys.solved.size() != L || (c.dp >= 0 && (uint32_t)c.dp != wf.h.dp) || (c.kn && c.kn != wf.h.herd) ||
-            (c.seed_given && c.seed != wf.h.seed) || (!dl.empty() && dl.size() != wf.h.engines) || !wf.h.engines || !wf.h.herd || !wf.h.per_thread || wf.h.herd % (64ull * wf.h.per_thread))
-            die("Recovery file was made with other settings");
-    } else { Config rc; rc.dir = c.dir; read_recovery(rc); }                      // (win.txt starts empty, as on the BSGS path; a resumed run appends to the one it has)
-    const auto t0 = Clock::now();
+    Prologue p(c);
+    printf("Kangaroo range [%s, %s], width 2^%.2f, %u public keys\n", hs::fe_to_hex(p.lo).c_str(), hs::fe_to_hex(p.hi).c_str(), std::log2((double)p.W), L);
+    ListMode mode(c, P);
+    p.complete(c, mode);                                                           // dp, kn, the jump mean and the launch length from W, as for one key
+    if (!p.go) return 0;
+    Shared sh(p);
+    mode.prepare(p, sh);
+    const Outcome o = run(c, p, sh, mode);
 
-    MultiKeyTable table(lo, W, P);
-    std::mutex tab_m;                                                              // table, assigner, win.txt
-    int found_n = 0;
-    std::map<std::string, std::vector<uint32_t>> same;                            // list positions that hold the same point
-    for (uint32_t k = 0; k < L; k++) same[hs::compress_pubkey(P[k])].push_back(k);
-    // a key is known: its KEY[n] block on the console and in win.txt at once, through key_lines as the BSGS path writes it
-    auto report = [&](uint32_t k) {
-        std::string console;
-        const std::string win = key_lines((int)k + 1, table.key(k), P[k], console);
-        fputs(console.c_str(), stdout);
-        fflush(stdout);
-        std::ofstream f(c.dir + "/win.txt", std::ios::app | std::ios::binary);
-        f << win;
-        found_n++;
-    };
-    // keys solved before any device is opened: P_k == a*G has no affine Q_k; it keeps its slot (G stands in, no kangaroo is assigned)
-    const Affine aG = hs::point_mul(hs::G, lo), naG = hs::affine_neg(aG);
-    std::vector<bool> presolved(L, false);
-    std::vector<uint8_t> qxy(64 * (size_t)L);
-    std::vector<Affine> Q(L);
-    for (uint32_t k = 0; k < L; k++) {
-        Q[k] = hs::point_add(P[k], naG);
-        if (Q[k].inf) { presolved[k] = true; table.presolve(k, lo); if (resume) found_n++; else report(k); Q[k] = hs::G; }
-        hs::affine_to_le(Q[k], &qxy[64 * (size_t)k], &qxy[64 * (size_t)k + 32]);
-    }
-    double elapsed_before = 0.0;
-    if (resume) {                                                                  // the file's solved keys are in win.txt already: counted, not written again
-        const uint32_t before = table.solved();
-        if (!table.restore(wf.table.data(), wf.h.table, wf.h.false_matches, wf.h.reseeds, wf.keys)) die("-kangaroo -wl: the table section of " + wl_path + " does not load");
-        std::vector<uint8_t>().swap(wf.table);
-        found_n += (int)(table.solved() - before);
-        elapsed_before = wf.h.elapsed;
-    }
-    const uint32_t open0 = L - table.solved();
-    if (!open0) { printf("Found %d of %u\n", found_n, L); return 0; }
-
-    std::vector<int> gpus;
-    {
-        int ngpu = 0;
-        CK(bsgs_dev_count(&ngpu));
-        if (ngpu <= 0) die("No GPU found");
-        if (c.devices.empty()) for (int i = 0; i < ngpu; i++) gpus.push_back(i);
-        else { std::stringstream ss(c.devices); std::string tok; while (std::getline(ss, tok, ',')) gpus.push_back(atoi(tok.c_str())); }
-    }
-    int cus = 256;
-    { bsgs_dev *d = nullptr; CK(bsgs_dev_open(gpus[0], &d)); bsgs_dev_cu_count(d, &cus); bsgs_dev_close(d); }
-    // dp, kn, the jump mean and the launch length from W, as for one key
-    if (resume && gpus.size() != wf.h.engines) die("Recovery file was made with other settings");
-    Plan pl = plan_herd(sqrtW, (uint32_t)gpus.size(), cus, resume ? (int)wf.h.dp : c.dp, c.kn);
-    if (resume) { pl.kn = wf.h.herd; pl.G = wf.h.per_thread; }                      // the plan of the run that saved, not this GPU's
-    const uint64_t kn = pl.kn;
-    if (kn > (1ull << 26)) die("-kn: at most 2^26 kangaroos per engine");
-    const double Nk = (double)kn * pl.engines, overhead = Nk * std::ldexp(1.0, (int)pl.dp);
-    pl.expected = 2.0 * sqrtW + overhead;
-    pl.S = (uint32_t)std::max(8.0, std::min(1024.0, pl.expected / Nk / 8.0));
-    pl.cap = (uint32_t)std::min<double>(1u << 22, 2.0 * (double)kn * pl.S / std::ldexp(1.0, (int)pl.dp) + 65536.0);
-    uint64_t seed = c.seed;
-    if (resume) seed = wf.h.seed;
-    else if (!c.seed_given) { std::random_device rd; seed = ((uint64_t)rd() << 32) ^ rd(); }
-    printf("Kangaroo: %u engine(s) x %llu kangaroos (%u per thread), -dp %u, %u steps per launch, -kseed 0x%llx\n", pl.engines, (unsigned long long)kn, pl.G, pl.dp, pl.S,
-           (unsigned long long)seed);
-    const double exp_lo = 2.0 * std::sqrt((double)open0 * Wd) + overhead, exp_hi = (double)open0 * 2.0 * sqrtW + overhead;
-    // (the give-up bound: 20 times L_open 2 sqrt(W) + overhead steps without a new key, L_open the keys open at that moment)
-    printf("Expected steps for %u keys: between 2^%.2f (2 sqrt(L W)) and 2^%.2f (L 2 sqrt(W)), DP overhead included\n", open0, std::log2(exp_lo), std::log2(exp_hi));
-
-    uint64_t rng = seed;
-    std::mutex rng_m;
-    const double mean = std::max(1.0, std::min(std::ldexp(1.0, 62), Nk * sqrtW / 4.0));
-    std::vector<uint64_t> js(BSGS_KANGAROO_JUMPS);
-    std::vector<uint8_t> jxy(64 * (size_t)BSGS_KANGAROO_JUMPS);
-    for (int j = 0; j < BSGS_KANGAROO_JUMPS; j++) {
-        const uint64_t span = (uint64_t)(2.0 * mean) > 1 ? (uint64_t)(2.0 * mean) - 1 : 1;
-        js[j] = 1 + splitmix64(rng) % span;
-        hs::affine_to_le(hs::point_mul(hs::G, hs::fe_from_u64(js[j])), &jxy[64 * j], &jxy[64 * j + 32]);
-    }
-    WorkHeader wh;                                                                 // what every save of this run shares
-    wh.version = WORK_VERSION_KEYS; wh.engines = pl.engines; wh.dp = pl.dp; wh.per_thread = pl.G; wh.herd = kn; wh.seed = seed;
-    wh.fingerprint = keys_fingerprint(P, lo, hi, wh);
-    const std::string work_path = c.dir + "/kangaroo.work", work_tmp = c.dir + "/kangaroo.temp";
-    const uint64_t half = kn / 2;                                                  // kangaroos [0, half) of an engine are tame, [half, kn) wild
-    Assigner asg(L, presolved, (kn - half) * pl.engines);
-    std::vector<std::vector<bsgs_kangaroo_state>> herds(pl.engines), saved(pl.engines);      // -wl: the file's herds; the herds as downloaded for a save
-    if (resume) {
-        std::vector<uint32_t> keys((kn - half) * pl.engines);
-        for (uint32_t e = 0; e < pl.engines; e++) {
-            herds[e].resize(kn);
-            memcpy(herds[e].data(), wf.herds[e].data(), kn * sizeof(bsgs_kangaroo_state));
-            std::vector<uint8_t>().swap(wf.herds[e]);
-            for (uint64_t i = half; i < kn; i++) {
-                const uint32_t k = (herds[e][i].flags >> BSGS_KANGAROO_KEY_SHIFT) & 0xFFFFu;
-                if (k >= L) die("-kangaroo -wl: a kangaroo of " + wl_path + " names key " + std::to_string(k));
-                keys[(uint64_t)e * (kn - half) + (i - half)] = k;
-            }
-        }
-        asg.restore(keys, table);
-    }
-    std::unique_ptr<Comb> comb;
-    if (c.cpuseed) comb.reset(new Comb());
-
-    std::atomic<bool> stop{false};
-    std::atomic<uint64_t> steps{0}, dps{0}, dropped{0};
-    std::mutex q_m; std::condition_variable q_cv;
-    std::deque<std::pair<uint32_t, std::vector<bsgs_kangaroo_record>>> queue;
-    std::vector<std::unique_ptr<std::mutex>> reseed_m;
-    std::vector<std::vector<uint32_t>> reseed(pl.engines);
-    std::vector<uint64_t> engine_records(pl.engines, 0);
-    for (uint32_t e = 0; e < pl.engines; e++) reseed_m.emplace_back(new std::mutex);
-    std::mutex err_m; std::string err;
-    if (resume) {
-        rng = wf.h.rng; steps = wf.h.steps; dps = wf.h.dps; dropped = wf.h.dropped;
-        for (uint32_t e = 0; e < pl.engines; e++) reseed[e] = wf.reseed[e];
-        printf("Resumed: %llu steps, %zu DPs, %u of %u keys solved\n", (unsigned long long)wf.h.steps, table.size(), table.solved(), L);
-    }
-    // saving ("a save is a consistent cut"): engines park between two launches with their herd downloaded
-    std::atomic<bool> save_req{false};
-    std::mutex save_m; std::condition_variable save_cv;
-    uint32_t parked = 0, running = 0;
-    bool collector_busy = false;                                                   // (under q_m) a batch has left the queue and is not in the table yet
-
-    // under tab_m.  The consequences of FOUND events: the block is written, equal points of the list are solved with it, the key's kangaroos start afresh
-    std::function<void(const std::vector<MultiKeyTable::Event> &)> on_events = [&](const std::vector<MultiKeyTable::Event> &ev) {
-        for (const MultiKeyTable::Event &x : ev) {
-            if (x.what != MultiKeyTable::FOUND) continue;
-            report(x.a);
-            asg.solved(x.a);
-            for (uint64_t w = 0; w < asg.keys().size(); w++) if (asg.keys()[w] == x.a) {
-                const uint32_t e = (uint32_t)(w / (kn - half));
-                std::lock_guard<std::mutex> lk(*reseed_m[e]);
-                reseed[e].push_back((uint32_t)(half + w % (kn - half)));
-            }
-            for (uint32_t o : same[hs::compress_pubkey(P[x.a])]) if (!table.known(o)) {
-                std::vector<MultiKeyTable::Event> more;
-                table.found(o, x.key, more);
-                on_events(more);
-            }
-        }
-        if (table.solved() == L) stop = true;
-    };
-    // offsets and keys of the kangaroos idx (local indices of engine e): under the stream's lock and the table's
-    auto draw = [&](uint32_t e, const std::vector<uint32_t> &idx, std::vector<uint32_t> &use, std::vector<i128> &d, std::vector<uint32_t> &fl, std::vector<uint32_t> &key) {
-        std::lock_guard<std::mutex> lt(tab_m);
-        std::lock_guard<std::mutex> lk(rng_m);
-        for (uint32_t i : idx) {
-            const bool wild = i >= half;
-            uint32_t k = 0;
-            if (wild && !asg.reseed((uint64_t)e * (kn - half) + (i - half), table, &k)) continue;      // no key is open: the kangaroo rests
-            use.push_back(i); fl.push_back(wild ? BSGS_KANGAROO_WILD : 0u); key.push_back(k);
-            d.push_back(herd_offset(rng, W, wild));
-        }
-    };
-    // Q_key + u G = infinity: k_key = a - u
-    auto infinite_start = [&](uint32_t k, i128 d) {
-        std::lock_guard<std::mutex> lt(tab_m);
-        if (table.known(k)) return;
-        std::vector<MultiKeyTable::Event> ev;
-        table.found(k, hs::sc_add(lo, sc_from_i128(-d)), ev);
-        on_events(ev);
-    };
-    // -kcpuseed: the same herd from the host's comb
-    auto host_states = [&](const std::vector<i128> &d, const std::vector<uint32_t> &fl, const std::vector<uint32_t> &key, std::vector<bsgs_kangaroo_state> &out, int64_t *first_inf) {
-        std::vector<hs::Jac> j(d.size());
-        for (size_t q = 0; q < d.size(); q++) {
-            const bool neg = d[q] < 0;
-            hs::Jac p = comb->mul(neg ? (u128)-d[q] : (u128)d[q]);
-            if (neg && !p.inf) p.y = hs::fe_neg(p.y);
-            if (fl[q]) p = hs::jac_add_affine(p, Q[key[q]]);
-            j[q] = p;
-        }
-        const std::vector<Affine> pts = hs::batch_to_affine(j);
-        out.resize(d.size());
-        *first_inf = -1;
-        for (size_t q = 0; q < d.size(); q++) {
-            bsgs_kangaroo_state &s = out[q];
-            memset(&s, 0, sizeof s);
-            if (!pts[q].inf) hs::affine_to_le(pts[q], s.x, s.y);
-            else if (*first_inf < 0) *first_inf = (int64_t)q;
-            memcpy(s.d, &d[q], 16);
-            s.flags = fl[q] | key[q] << BSGS_KANGAROO_KEY_SHIFT | (pts[q].inf ? BSGS_KANGAROO_DEAD : 0u);
-        }
-    };
-    // initial herds: offsets in engine order from the seeded stream, whoever computes the points
-    std::vector<std::vector<i128>> off0(pl.engines);
-    if (!resume) for (uint32_t e = 0; e < pl.engines; e++) { off0[e].resize(kn); for (uint64_t i = 0; i < kn; i++) off0[e][i] = herd_offset(rng, W, i >= half); }
-
-    auto engine = [&](uint32_t e) {
-        bsgs_dev *dev = nullptr;
-        auto bad = [&](const char *what) { std::lock_guard<std::mutex> lk(err_m); if (err.empty()) err = std::string(what) + ": " + bsgs_last_error(); stop = true; };
-        // one seed call: by range (idx empty) or by list; a start at infinity solves its key and the kangaroo is seeded again next round
-        auto seed_call = [&](const std::vector<uint32_t> &idx, const std::vector<i128> &d, const std::vector<uint32_t> &fl, const std::vector<uint32_t> &key) -> bool {
-            uint32_t ninf = 0, first = 0;
-            if (c.cpuseed) {
-                std::vector<bsgs_kangaroo_state> st;
-                int64_t fi;
-                host_states(d, fl, key, st, &fi);
-                if ((idx.empty() ? bsgs_kangaroo_upload(dev, 0, (uint32_t)st.size(), st.data()) : bsgs_kangaroo_upload_list(dev, idx.data(), (uint32_t)idx.size(), st.data())) != BSGS_OK) { bad("bsgs_kangaroo_upload"); return false; }
-                if (fi >= 0) { ninf = 1; first = (uint32_t)fi; }
-            } else if (bsgs_kangaroo_seed_keys(dev, idx.empty() ? nullptr : idx.data(), 0, (uint32_t)d.size(), (const uint8_t *)d.data(), fl.data(), key.data(), &ninf, &first) != BSGS_OK) { bad("bsgs_kangaroo_seed_keys"); return false; }
-            if (ninf) {
-                if (fl[first]) infinite_start(key[first], d[first]);
-                std::lock_guard<std::mutex> lk(*reseed_m[e]);
-                reseed[e].push_back(idx.empty() ? first : idx[first]);
-            }
-            return true;
-        };
-        if (bsgs_dev_open(gpus[e], &dev) != BSGS_OK) { bad("bsgs_dev_open"); return; }
-        bool ok = bsgs_kangaroo_setup(dev, jxy.data(), js.data(), pl.dp, (uint32_t)kn, pl.G, pl.cap) == BSGS_OK;
-        if (!ok) bad("bsgs_kangaroo_setup");
-        if (ok && bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) { bad("bsgs_kangaroo_set_keys"); ok = false; }
-        if (ok && resume) {
-            if (bsgs_kangaroo_upload(dev, 0, (uint32_t)kn, herds[e].data()) != BSGS_OK) { bad("bsgs_kangaroo_upload"); ok = false; }
-            std::vector<bsgs_kangaroo_state>().swap(herds[e]);
-        } else if (ok) {
-            const auto ts = Clock::now();
-            std::vector<uint32_t> fl(kn), key(kn, 0);
-            for (uint64_t i = 0; i < kn; i++) { fl[i] = i >= half ? BSGS_KANGAROO_WILD : 0u; if (i >= half) key[i] = asg.key((uint64_t)e * (kn - half) + (i - half)); }
-            ok = seed_call({}, off0[e], fl, key);
-            std::vector<i128>().swap(off0[e]);
-            std::lock_guard<std::mutex> lk(err_m);
-            printf("[startup] %-44s %.3fs\n", ((c.cpuseed ? "herds (host), engine " : "herds (GPU), engine ") + std::to_string(e)).c_str(), since(ts));
-        }
-        std::vector<bsgs_kangaroo_record> recs(pl.cap);
-        while (ok && !stop.load()) {
-            std::vector<uint32_t> rs;
-            { std::lock_guard<std::mutex> lk(*reseed_m[e]); rs.swap(reseed[e]); }
-            if (!rs.empty()) {
-                std::sort(rs.begin(), rs.end());
-                rs.erase(std::unique(rs.begin(), rs.end()), rs.end());
-                std::vector<uint32_t> use, fl, key;
-                std::vector<i128> d;
-                draw(e, rs, use, d, fl, key);
-                if (!use.empty() && !seed_call(use, d, fl, key)) break;
-                if (stop.load()) break;
-            }
-            uint32_t n = 0;
-            uint64_t drop = 0;
-            if (bsgs_kangaroo_run(dev, pl.S, recs.data(), pl.cap, &n, &drop, nullptr) != BSGS_OK) { bad("bsgs_kangaroo_run"); break; }
-            const uint64_t total = (steps += kn * pl.S);
-            dropped += drop;
-            { std::lock_guard<std::mutex> lk(q_m); queue.emplace_back(e, std::vector<bsgs_kangaroo_record>(recs.begin(), recs.begin() + n)); }
-            q_cv.notify_one();
-            if (c.ksteps && total >= c.ksteps) stop = true;
-            if (save_req.load() && !stop.load()) {                       // between two launches: the herd as it stands, then wait for the file
-                saved[e].resize(kn);
-                if (bsgs_kangaroo_download(dev, 0, (uint32_t)kn, saved[e].data()) != BSGS_OK) { bad("bsgs_kangaroo_download"); ok = false; break; }
-                std::unique_lock<std::mutex> lk(save_m);
-                parked++;
-                save_cv.notify_all();
-                while (save_req.load() && !stop.load()) save_cv.wait_for(lk, std::chrono::milliseconds(100));
-                parked--;
-            }
-        }
-        bool all_solved;
-        { std::lock_guard<std::mutex> lt(tab_m); all_solved = table.solved() == L; }
-        if (ok && dev && !all_solved) {                                  // the run stops with keys open: the herd goes into the last save
-            saved[e].resize(kn);
-            if (bsgs_kangaroo_download(dev, 0, (uint32_t)kn, saved[e].data()) != BSGS_OK) { bad("bsgs_kangaroo_download"); saved[e].clear(); }
-        }
-        if (dev) bsgs_dev_close(dev);
-        std::lock_guard<std::mutex> lk(save_m);
-        running--;
-        save_cv.notify_all();
-    };
-    // the work file from the state as it stands: callers make sure that no engine walks and the collector's queue is empty
-    auto write_state = [&]() {
-        std::lock_guard<std::mutex> lt(tab_m);
-        WorkHeader h = wh;
-        h.rng = rng; h.steps = steps.load(); h.dps = dps.load(); h.dropped = dropped.load();
-        h.false_matches = table.false_matches(); h.reseeds = table.reseeds(); h.table = table.size();
-        h.elapsed = elapsed_before + since(t0);
-        std::vector<uint8_t> entries;
-        entries.reserve(32 * table.size());
-        table.write_entries(entries);
-        WorkKeys wk;
-        table.write_keys(wk);
-        std::vector<const std::vector<bsgs_kangaroo_state> *> hp;
-        std::vector<std::vector<uint32_t>> rs(pl.engines);
-        for (uint32_t e = 0; e < pl.engines; e++) { hp.push_back(&saved[e]); std::lock_guard<std::mutex> lk(*reseed_m[e]); rs[e] = reseed[e]; }
-        if (!write_work_file(work_path, work_tmp, h, entries, hp, rs, &wk)) fprintf(stderr, "WARNING: cannot write %s\n", work_path.c_str());
-    };
-    std::atomic<bool> engines_done{false};
-    std::thread collector([&]() {
-        for (;;) {
-            std::pair<uint32_t, std::vector<bsgs_kangaroo_record>> b;
-            {
-                std::unique_lock<std::mutex> lk(q_m);
-                collector_busy = false;
-                q_cv.wait_for(lk, std::chrono::milliseconds(100), [&] { return !queue.empty() || engines_done.load(); });
-                if (queue.empty()) { if (engines_done.load()) return; continue; }
-                b = std::move(queue.front());
-                queue.pop_front();
-                collector_busy = true;
-            }
-            std::lock_guard<std::mutex> lt(tab_m);
-            if (table.solved() == L) continue;
-            engine_records[b.first] += b.second.size();
-            std::vector<MultiKeyTable::Event> ev;
-            for (const bsgs_kangaroo_record &r : b.second) {
-                u128 d;
-                memcpy(&d, r.d, 16);
-                ev.clear();
-                table.add(r.x, d, (uint32_t)(b.first * kn + r.kangaroo), r.flags, ev);
-                if (!(r.flags & BSGS_KANGAROO_DEAD)) dps++;
-                for (const MultiKeyTable::Event &x : ev) if (x.what == MultiKeyTable::RESEED) { std::lock_guard<std::mutex> lk(*reseed_m[b.first]); reseed[b.first].push_back(r.kangaroo); }
-                on_events(ev);
-            }
-        }
-    });
-    multi_signalled = 0;
-    signal(SIGINT, multi_on_signal);
-    signal(SIGTERM, multi_on_signal);
-    std::vector<std::thread> th;
-    running = pl.engines;
-    for (uint32_t e = 0; e < pl.engines; e++) th.emplace_back(engine, e);
-    auto last_t = Clock::now(), last_save = Clock::now();
-    uint64_t last_steps = steps.load(), steps_mark = last_steps;
-    uint32_t last_solved = table.solved();
-    bool gave_up = false, interrupted = false;
-    while (!stop.load()) {
-        std::this_thread::sleep_for(std::chrono::milliseconds(100));
-        const auto now = Clock::now();
-        if (multi_signalled) { interrupted = true; stop = true; save_cv.notify_all(); break; }
-        if (std::chrono::duration<double>(now - last_t).count() >= 2.0) {
-            const uint64_t st = steps.load();
-            uint32_t solved;
-            { std::lock_guard<std::mutex> lt(tab_m); solved = table.solved(); }
-            printf("\r[%u] %.3e steps/s  steps 2^%.2f of expected 2^%.2f..2^%.2f  solved %u/%u  DPs %llu  %.0fs   ", pl.engines, (st - last_steps) / std::chrono::duration<double>(now - last_t).count(),
-                   st ? std::log2((double)st) : 0.0, std::log2(exp_lo), std::log2(exp_hi), solved, L, (unsigned long long)dps.load(), since(t0));
-            fflush(stdout);
-            last_steps = st; last_t = now;
-        }
-        {                                                                // give up: 20 times one key's expectation for every key still open, counted from the last key found
-            uint32_t solved_now;
-            { std::lock_guard<std::mutex> lt(tab_m); solved_now = table.solved(); }
-            if (solved_now != last_solved) { last_solved = solved_now; steps_mark = steps.load(); }
-            if ((double)(steps.load() - steps_mark) > 20.0 * ((double)(L - solved_now) * 2.0 * sqrtW + overhead)) { gave_up = true; stop = true; }
-        }
-        if (!stop.load() && std::chrono::duration<double>(now - last_save).count() >= (double)c.wt) {
-            // -wt: every engine parks between two launches with its herd downloaded; the collector empties the queue; then table, keys, links, stream, herds
-            // and re-seed lists belong to one moment of the search
-            const auto ts = Clock::now();
-            save_req = true;
-            {
-                std::unique_lock<std::mutex> lk(save_m);
-                while (parked != running && !stop.load() && !multi_signalled) save_cv.wait_for(lk, std::chrono::milliseconds(100));
-            }
-            for (;;) {
-                { std::lock_guard<std::mutex> lk(q_m); if ((queue.empty() && !collector_busy) || stop.load()) break; }
-                std::this_thread::sleep_for(std::chrono::milliseconds(1));
-            }
-            bool all_parked;
-            { std::lock_guard<std::mutex> lk(save_m); all_parked = parked == pl.engines; }
-            if (all_parked && !stop.load()) { write_state(); printf("\n[save] %s in %.2fs\n", work_path.c_str(), since(ts)); }
-            { std::lock_guard<std::mutex> lk(save_m); save_req = false; }
-            save_cv.notify_all();
-            last_save = Clock::now();
-        }
-    }
-    save_cv.notify_all();
-    for (auto &t : th) t.join();
-    engines_done = true;
-    q_cv.notify_all();
-    collector.join();
-    signal(SIGINT, SIG_DFL);
-    signal(SIGTERM, SIG_DFL);
-    if (!err.empty()) die(err);
-    const bool all = table.solved() == L;
-    const bool budget = !all && !gave_up && !interrupted && c.ksteps && steps.load() >= c.ksteps;
-    if (all) remove(work_path.c_str());                                            // a stale file never outlives its job
-    else {
-        bool have = true;
-        for (uint32_t e = 0; e < pl.engines; e++) have = have && saved[e].size() == kn;
-        if (have) write_state();                                                   // engines joined, queue drained: the state is final
-    }
-    if (!all) {
-        if (gave_up) printf("\nKangaroo: %u of %u keys open after 20 times the expected steps (are the keys in the range?)\n", L - table.solved(), L);
-        else printf("\nKangaroo: stopped after %llu steps (%s), %u of %u keys open\n", (unsigned long long)steps.load(), budget ? "-ksteps" : "signal",
-                    L - table.solved(), L);
-    }
-    printf("Job time %.2fs, %.3e kangaroo steps, %llu DPs (%zu in the table, %llu dropped), %llu false matches, %llu re-seeds, %llu links kept, %llu links resolved\n", elapsed_before + since(t0),
-           (double)steps.load(), (unsigned long long)dps.load(), table.size(), (unsigned long long)dropped.load(), (unsigned long long)table.false_matches(),
+    const MultiKeyTable &table = *mode.table;
+    if (o == GAVE_UP) printf("\nKangaroo: %u of %u keys open after 20 times the expected steps (are the keys in the range?)\n", L - table.solved(), L);
+    else if (o != DONE) printf("\nKangaroo: stopped after %llu steps (%s), %u of %u keys open\n", (unsigned long long)sh.steps.load(), o == BUDGET ? "-ksteps" : "signal",
+                               L - table.solved(), L);
+    printf("Job time %.2fs, %.3e kangaroo steps, %llu DPs (%zu in the table, %llu dropped), %llu false matches, %llu re-seeds, %llu links kept, %llu links resolved\n", p.elapsed_before + since(p.t0),
+           (double)sh.steps.load(), (unsigned long long)sh.dps.load(), table.size(), (unsigned long long)sh.dropped.load(), (unsigned long long)table.false_matches(),
            (unsigned long long)table.reseeds(), (unsigned long long)table.links_kept(), (unsigned long long)table.links_resolved());
-    for (uint32_t e = 0; e < pl.engines; e++) printf("Engine %u (GPU #%d): %llu records\n", e, gpus[e], (unsigned long long)engine_records[e]);
-    printf("Found %d of %u\n", found_n, L);
+    for (uint32_t e = 0; e < p.pl.engines; e++) printf("Engine %u (GPU #%d): %llu records\n", e, p.gpus[e], (unsigned long long)sh.engine_records[e]);
+    printf("Found %d of %u\n", mode.found_n, L);
     fflush(stdout);
-    return all ? 0 : (budget || interrupted) ? 3 : 1;
+    return o == DONE ? 0 : (o == BUDGET || o == INTERRUPTED) ? 3 : 1;
 }

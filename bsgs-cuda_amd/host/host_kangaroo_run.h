@@ -1,0 +1,87 @@
+// host_kangaroo_run.h -- the one prologue and the one run loop of bsgs_mi355x -kangaroo (host_kangaroo_run.cpp), and the seam the two modes
+// stand behind: KeyMode (host_kangaroo.cpp: one public key, plain and -ksym) and ListMode (host_kangaroo_multi.cpp: -infile).  The driver owns the engine
+// threads, the collector, the monitor with the save handshake, the signals, the shutdown and the work file's common part; a Mode owns its table of
+// distinguished points, how a kangaroo is started and what a record means.
+#pragma once
+#include "host_kangaroo.h"
+
+namespace kang {
+class Mode;
+
+// what a run works from: the range, the work file of -wl, the devices, the completed plan, the seed and the jump table
+struct Prologue {
+    explicit Prologue(const KangConfig &c);        // the range: validated, or the run ends here
+    // -wl (read and checked before any device is looked for), mode.before_devices, the device list, the plan, the seed, the jump table; go = false: the
+    // mode found nothing left to search
+    void complete(const KangConfig &c, Mode &mode);
+    Scalar lo, hi;
+    u128 W;
+    double sqrtW;
+    bool resume = false, go = true;
+    std::string wl_path, work_path, work_tmp;
+    WorkFile wf;                                   // -wl: header, key list, re-seed lists; the table until the mode has restored it
+    std::vector<std::vector<bsgs_kangaroo_state>> herds;      // per engine, the herd to upload: the file's, or what a mode computed before the engines start
+    double elapsed_before = 0.0;
+    Clock::time_point t0 = Clock::now();           // what "Job time" counts from: each mode sets it where it always did
+    std::vector<int> gpus;
+    Plan pl;
+    WorkHeader wh;                                 // what every save of this run shares
+    std::vector<uint64_t> js;                      // jump table: s_j uniform in [1, 2m), m = scale * N_k sqrt(W) / 4 (at most 2^62): a function of the seed
+    std::vector<uint8_t> jxy;                      // and the plan, never saved
+    uint64_t rng;                                  // the seeded stream behind the jump table (-wl: the file's)
+};
+
+// what the engines, the collector, the saver and the mode share
+struct Shared {
+    explicit Shared(const Prologue &p);
+    std::atomic<bool> stop{false};
+    std::atomic<uint64_t> steps{0}, dps{0}, dropped{0};
+    std::mutex rng_m;
+    uint64_t rng;                                  // the seeded stream: initial herds in engine order, then every re-seed
+    std::mutex tab_m;                              // the mode's table and what hangs on it: held around record(), done(), give_up(), status() and save()
+    std::mutex q_m; std::condition_variable q_cv;
+    std::deque<std::pair<uint32_t, std::vector<bsgs_kangaroo_record>>> queue;     // (engine, records of one launch)
+    bool collector_busy = false;                   // (under q_m) a batch has left the queue and is not in the table yet
+    std::vector<std::unique_ptr<std::mutex>> reseed_m;
+    std::vector<std::vector<uint32_t>> reseed;     // per engine: kangaroos (local index) to start afresh
+    std::vector<uint64_t> engine_records;
+    std::mutex err_m; std::string err;
+    // saving ("a save is a consistent cut"): engines park between two launches with their herd downloaded
+    std::atomic<bool> save_req{false};
+    std::mutex save_m; std::condition_variable save_cv;
+    uint32_t parked = 0, running = 0;              // (under save_m) engines waiting for the save to end / engine threads alive
+    std::vector<std::vector<bsgs_kangaroo_state>> saved;      // per engine: the herd as downloaded at the last park or at the end
+    Clock::time_point ended;                       // when the engines and the collector had ended, before the last save
+    void push_reseed(uint32_t e, uint32_t i) { std::lock_guard<std::mutex> lk(*reseed_m[e]); reseed[e].push_back(i); }
+};
+
+class Mode {
+public:
+    virtual ~Mode() {}
+    // what the prologue asks: the work file's version, the floor of the launch length, the jump table's size and scale, how a refused -wl is worded
+    uint32_t version = WORK_VERSION, jumps = BSGS_KANGAROO_JUMPS;
+    double min_launch = 8.0, jumpscale = 1.0;
+    const char *wl_flag = "-kangaroo -wl", *wl_kind = "a kangaroo.work file";
+    const char *herd_label = "herds (GPU), engine ";                  // the [startup] line of a herd seeded in its engine's thread
+    virtual std::string fingerprint(const Prologue &p, const WorkHeader &h) const = 0;
+    // between the work file and the devices: the mode's own resume checks ("Recovery file was made with other settings"), its header fields, its first
+    // lines, the keys known without a search; false: nothing is left to search
+    virtual bool before_devices(Prologue &p) = 0;
+    // in an engine's thread; nullptr, or the name of the call that failed
+    virtual const char *setup(bsgs_dev *dev) = 0;
+    // starts the kangaroos idx of engine e (empty: the whole herd, from the offsets drawn in engine order before the run); draws under the locks it needs
+    virtual const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) = 0;
+    // under sh.tab_m.  One record of engine e into the table: kangaroos to start afresh go on sh's lists, a finished search sets sh.stop; false: the rest of
+    // the batch is not looked at
+    virtual bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &sh) = 0;
+    virtual bool done() const = 0;
+    virtual bool give_up(uint64_t steps) = 0;
+    virtual void status(double rate, uint64_t steps, uint64_t dps) const = 0;
+    // the mode's part of a work file: the table's entries and counters, its own header fields; the key list's state or nullptr
+    virtual const WorkKeys *save(WorkHeader &h, std::vector<uint8_t> &entries) = 0;
+};
+
+enum Outcome { DONE, GAVE_UP, BUDGET, INTERRUPTED, ENDED };           // ENDED: stopped for none of the other reasons
+// engines, collector, monitor, shutdown and the last save; the mode turns the outcome into its closing text and exit code
+Outcome run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode);
+}  // namespace kang

@@ -135,7 +135,7 @@ int selftest(int argc, char **argv)
                 J.inflight.push_back(v); J.inflight_valid.push_back(valid);
             }
             save_checkpoint(R.cfg, J.listpos, "selftest", J.checkpoint_counter());
-        } else if (a[i] == "kangaroo-work") {                               // the header of a work file (host_kangaroo.cpp)
+        } else if (a[i] == "kangaroo-work") {                               // the header of a work file (host_kangaroo_work.cpp)
             return kangaroo_work_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-table-roundtrip") {                    // the table through a work file in the middle of a record stream
             return kangaroo_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));

@@ -16,7 +16,7 @@ def splitmix64(state):
 
 
 class Stream:
-    """the seeded stream herds and jump tables are drawn from (host_kangaroo.cpp)"""
+    """the seeded stream herds and jump tables are drawn from (host_kangaroo.h; the jump table: host_kangaroo_run.cpp)"""
 
     def __init__(self, seed):
         self.s = seed & 0xFFFFFFFFFFFFFFFF

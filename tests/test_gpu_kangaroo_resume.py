@@ -1,4 +1,4 @@
-"""GPU: bsgs_mi355x -kangaroo with herds seeded on the GPU, the work file kangaroo.work, -ksteps and -wl (host_kangaroo.cpp), through the
+"""GPU: bsgs_mi355x -kangaroo with herds seeded on the GPU, the work file kangaroo.work, -ksteps and -wl (host_kangaroo_run.cpp, host_kangaroo_work.cpp), through the
 command line.  One host process at a time, each under its own time limit."""
 import math
 import os

@@ -1,4 +1,4 @@
-"""CPU: the version-2 kangaroo work file of -ksym (host_kangaroo.cpp).  The symmetric table goes through a version-2 file at every split of
+"""CPU: the version-2 kangaroo work file of -ksym (host_kangaroo_work.cpp).  The symmetric table goes through a version-2 file at every split of
 scripted record streams and still gives the model's verdicts; the file holds the model's table at the split; each mode refuses the other's file."""
 import os
 import subprocess

@@ -1,4 +1,4 @@
-"""CPU: the kangaroo work file (host_kangaroo.cpp; layout in DESIGN.md 10).  The host's table of distinguished points goes through a work file at every
+"""CPU: the kangaroo work file (host_kangaroo_work.cpp; layout in DESIGN.md 10).  The host's table of distinguished points goes through a work file at every
 split point of scripted record streams and still gives the model's verdicts for the undivided stream; the file's header and table section hold what the model
 has at the split; files that are truncated, foreign or made with other settings are refused."""
 import os
