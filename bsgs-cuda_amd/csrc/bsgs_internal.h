@@ -14,7 +14,8 @@ int bsgs_fail(int code, const char *fmt, ...);
     } while (0)
 #define fail bsgs_fail
 
-// kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip, kangaroo_seed_keys.hip: the comb table, the staging of a seed call and the key list
+// kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip, kangaroo_seed_keys.hip: the comb table, the staging of a seed call and the key list;
+// kangaroo_verify.hip: the one Q of a call and the list of failures
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
     u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
@@ -29,6 +30,9 @@ struct bsgs_kangaroo {
     uint32_t R = 0;                        // bsgs_kangaroo_setup_sym: jump points of the symmetric walk (0: the plain walk)
     u32x4 *keys = nullptr;                 // bsgs_kangaroo_set_keys: n_keys affine points Q_k, x || y (64 bytes each)
     uint32_t n_keys = 0;
+    u32x4 *verify_q = nullptr;             // bsgs_kangaroo_verify*: the call's one Q, x || y (64 bytes)
+    u32 *verify_out = nullptr;             // {positions that failed, then the first verify_cap of them}
+    uint32_t verify_cap = 0;
 };
 
 struct bsgs_dev {

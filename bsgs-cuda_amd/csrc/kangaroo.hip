@@ -331,7 +331,7 @@ void bsgs_kangaroo_release(bsgs_dev *d)
     bsgs_kangaroo *k = d->kangaroo;
     if (!k) return;
     for (void *p : {(void *)k->st, (void *)k->chain, (void *)k->table, (void *)k->staging, (void *)k->flags, (void *)k->rec, (void *)k->idx, (void *)k->comb,
-                    (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out, (void *)k->mark, (void *)k->keys})
+                    (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out, (void *)k->mark, (void *)k->keys, (void *)k->verify_q, (void *)k->verify_out})
         if (p) (void)hipFree(p);
     if (k->rec_host) (void)hipHostFree(k->rec_host);
     delete k;

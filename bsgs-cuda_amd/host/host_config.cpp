@@ -76,6 +76,7 @@ void usage(const Config &c)
            "             and once more when the run stops without the key; the file is removed when the key is found\n"
            "-wl FILE     Kangaroo: continue from a kangaroo.work file: same -pb -pk -pke and number of -d entries; -dp -kn -kseed are taken from the file\n"
            "-ksteps N    Kangaroo: stop once N steps were walked in total (checked after each launch), save kangaroo.work, exit code 3 (SIGINT / SIGTERM do the same)\n"
+           "-noverify    Kangaroo: skip the check of every kangaroo (and, at -wl, of every saved table entry) against its offset on the GPU: at -wl before the first step, and before every save\n"
            "-kcpuseed    Kangaroo: compute the kangaroos' start points on the host CPU instead of the GPU (same herd; for cross-checks)\n"
            "-ksym        Kangaroo: the symmetric walk (negation map: P and -P are one point of the walk; wild-wild collisions solve too; cycles are retired and re-seeded)\n"
            "-kjumps R    Kangaroo -ksym: jump points, a power of two 64..4096 (default 1024)\n"

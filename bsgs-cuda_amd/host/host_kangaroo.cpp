@@ -274,6 +274,7 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
         else if (a == "-ksym") c.sym = true;
+        else if (a == "-noverify") c.verify = false;
         else if (a == "-kjumps") { c.jumps = (uint32_t)strtoul(next().c_str(), nullptr, 10); if (c.jumps < 64 || c.jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (c.jumps & (c.jumps - 1))) die("-kjumps must be a power of two, 64..4096"); }
         else if (a == "-kjumpscale") { c.jumpscale = atof(next().c_str()); if (!(c.jumpscale >= 1.0 / 64 && c.jumpscale <= 64.0)) die("-kjumpscale must be 1/64..64"); }
         else if (a == "-w" || a == "-htsz" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table)");
@@ -324,6 +325,8 @@ struct KeyMode : Mode {
         base = c.sym ? hs::sc_add(p.lo, hs::sc_from_u128(p.W / 2)) : p.lo;
         Q = hs::point_add(P, hs::affine_neg(hs::point_mul(hs::G, base)));
         hs::affine_to_le(Q, qxy, qxy + 32);
+        verify_q = qxy;
+        if (Q.inf) verify_skip = "the key is -pk itself, there is no affine Q to check a herd against";
         jobs.reset(new JobList({c.pub}, Recovery(), c.dir, [](int, const std::string &, const Scalar &) {}));      // win.txt as the BSGS path writes it
         { Config rc; rc.dir = c.dir; read_recovery(rc); }                                                  // (win.txt starts empty, as there: the key was not found yet)
         jobs->open_lanes(1);
@@ -427,6 +430,7 @@ struct KeyMode : Mode {
         if (v == KangarooTable::RESEED) sh.push_reseed(e, r.kangaroo);
         return true;
     }
+    uint32_t entry_flags(uint32_t type) const override { return (type & 1u ? BSGS_KANGAROO_WILD : 0u) | (type & 2u ? BSGS_KANGAROO_NEG : 0u); }      // 0 tame, 1 wild, 3 wild with NEG
     bool done() const override { return found.load(); }
     bool give_up(uint64_t steps) override { return (double)steps > 20.0 * pro->pl.expected; }
     void status(double rate, uint64_t st, uint64_t dps) const override

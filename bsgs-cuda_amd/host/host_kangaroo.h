@@ -63,6 +63,7 @@ struct KangConfig {
     bool sym = false;                              // -ksym: the symmetric walk (negation map)
     uint32_t jumps = 0;                            // -kjumps: jump points of the symmetric walk (default 1024; resumed: from the work file)
     double jumpscale = 0.0;                        // -kjumpscale: mean jump = scale * N_k sqrt(W) / 4 (default KSYM_JUMPSCALE; resumed: from the work file)
+    bool verify = true;                            // -noverify: herds and the saved table are not checked against their offsets (at -wl, before every save)
 };
 KangConfig parse_kangaroo_args(int argc, char **argv);
 

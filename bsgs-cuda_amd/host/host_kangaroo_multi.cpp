@@ -440,6 +440,8 @@ struct ListMode : Mode {
         on_events(ev);
         return true;
     }
+    // (verify_q stays null: the engines hold the key list)  owner 0 tame, 1 + k a wild kangaroo of key k
+    uint32_t entry_flags(uint32_t owner) const override { return owner ? BSGS_KANGAROO_WILD | (owner - 1u) << BSGS_KANGAROO_KEY_SHIFT : 0u; }
     bool done() const override { return table->solved() == L; }
     // give up: 20 times one key's expectation for every key still open, counted from the last key found
     bool give_up(uint64_t steps) override

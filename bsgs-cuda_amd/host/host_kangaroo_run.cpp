@@ -70,8 +70,10 @@ void Prologue::complete(const KangConfig &c, Mode &mode)
             (!dl.empty() && dl.size() != wf.h.engines) || !wf.h.engines || !wf.h.herd || !wf.h.per_thread || wf.h.herd % (64ull * wf.h.per_thread))
             die("Recovery file was made with other settings");
         elapsed_before = wf.h.elapsed;
+        if (c.verify) check_table = wf.table;                          // (the mode restores its table from wf.table and lets go of it)
     }
     if (!mode.before_devices(*this)) { go = false; return; }
+    if (mode.verify_skip) std::vector<uint8_t>().swap(check_table);
 
     int ngpu = 0;
     CK(bsgs_dev_count(&ngpu));
@@ -130,12 +132,67 @@ namespace {
 volatile sig_atomic_t signalled = 0;
 void on_signal(int) { signalled = 1; }
 
+// TEST BUILD ONLY (bsgs_mi355x_test, -DBSGS_TEST_HOOKS; the shipped host has no such hook): BSGS_TEST_CORRUPT_KANGAROO=i flips bit 0 of the offset of kangaroo
+// i of engine 0 after the first launch -- the run must then stop at the verification before its next save
+void test_corrupt_kangaroo(bsgs_dev *dev, uint64_t kn)
+{
+#ifdef BSGS_TEST_HOOKS
+    const char *v = getenv("BSGS_TEST_CORRUPT_KANGAROO");
+    if (!v) return;
+    const uint32_t i = (uint32_t)strtoul(v, nullptr, 10);
+    if (i >= kn) return;
+    fprintf(stderr, "BSGS_TEST_CORRUPT_KANGAROO=%s: TEST HOOK -- bit 0 of the offset of kangaroo %u of engine 0 is flipped (this run must stop before it saves)\n", v, i);
+    bsgs_kangaroo_state s;
+    CK(bsgs_kangaroo_download(dev, i, 1, &s));
+    s.d[0] ^= 1u;
+    CK(bsgs_kangaroo_upload_list(dev, &i, 1, &s));
+#else
+    (void)dev; (void)kn;
+#endif
+}
+
+// every kangaroo of the device's herd against sigma*Q + d*G (bsgs_kangaroo_verify; the herd is only read): 0 all stand at their offsets, 1 *at is the
+// lowest-numbered one found that does not, -1 the call failed
+int herd_check(bsgs_dev *dev, const Mode &mode, uint64_t kn, uint32_t *at)
+{
+    uint32_t n_bad = 0;
+    if (bsgs_kangaroo_verify(dev, mode.verify_q, 0, (uint32_t)kn, &n_bad, at, 1) != BSGS_OK) return -1;
+    return n_bad ? 1 : 0;
+}
+// -wl: the file's table entries through bsgs_kangaroo_verify_points, 2^20 at a time: as herd_check, *at the entry's position in the file
+int table_check(bsgs_dev *dev, const Mode &mode, const std::vector<uint8_t> &entries, uint64_t *at)
+{
+    const uint64_t D = entries.size() / 32, step = 1u << 20;
+    std::vector<uint8_t> d(16 * std::min(D, step));
+    std::vector<uint32_t> fl(std::min(D, step));
+    std::vector<uint64_t> x(std::min(D, step));
+    for (uint64_t pos = 0; pos < D; pos += step) {
+        const uint32_t m = (uint32_t)std::min(D - pos, step);
+        for (uint32_t k = 0; k < m; k++) {                             // an entry: low 64 bits of x, d, kangaroo, type or owner
+            const uint8_t *en = &entries[32 * (pos + k)];
+            uint32_t word;
+            memcpy(&x[k], en, 8); memcpy(&d[16 * (size_t)k], en + 8, 16); memcpy(&word, en + 28, 4);
+            fl[k] = mode.entry_flags(word);
+        }
+        uint32_t n_bad = 0, first = 0;
+        if (bsgs_kangaroo_verify_points(dev, mode.verify_q, m, d.data(), fl.data(), x.data(), &n_bad, &first, 1) != BSGS_OK) return -1;
+        if (n_bad) { *at = pos + first; return 1; }
+    }
+    return 0;
+}
+
 // one engine: all calls for a device from the thread that opened it
 void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
 {
     const uint64_t kn = p.pl.kn;
+    const bool check = c.verify && !mode.verify_skip;                  // herds and the saved table vouch for themselves ("verification")
     bsgs_dev *dev = nullptr;
-    auto bad = [&](const char *what) { std::lock_guard<std::mutex> lk(sh.err_m); if (sh.err.empty()) sh.err = std::string(what) + ": " + bsgs_last_error(); sh.stop = true; };
+    auto end_with = [&](const std::string &msg) { std::lock_guard<std::mutex> lk(sh.err_m); if (sh.err.empty()) sh.err = msg; sh.failed = true; sh.stop = true; };
+    auto bad = [&](const char *what) { end_with(std::string(what) + ": " + bsgs_last_error()); };
+    auto verified = [&](const char *lead, const std::string &what, Clock::time_point ts) {
+        std::lock_guard<std::mutex> lk(sh.err_m);
+        printf("%s[verify] %s %.3fs\n", lead, what.c_str(), since(ts));
+    };
     const char *failed = nullptr;
     if (bsgs_dev_open(p.gpus[e], &dev) != BSGS_OK) failed = "bsgs_dev_open";
     else if ((failed = mode.setup(dev)) != nullptr) {}
@@ -149,8 +206,34 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
             printf("[startup] %-44s %.3fs\n", (mode.herd_label + std::to_string(e)).c_str(), since(ts));
         }
     }
-    const bool ok = failed == nullptr;                                 // the device holds a herd that can walk
+    bool ok = failed == nullptr;                                       // the device holds a herd that can walk
     if (!ok) bad(failed);
+    // -wl: what was uploaded is checked before anything walks -- every kangaroo of every engine, and on the first engine's device every entry of the
+    // saved table; a mismatch ends the run with the file as it is
+    if (p.resume && check) {
+        if (ok) {
+            auto ts = Clock::now();
+            uint32_t at = 0;
+            const int rc = herd_check(dev, mode, kn, &at);
+            if (rc < 0) bad("bsgs_kangaroo_verify");
+            else if (rc) end_with("Recovery file is damaged: kangaroo " + std::to_string(at) + " of engine " + std::to_string(e) + " does not stand at its offset");
+            else verified("", "herd " + std::to_string(e) + ": " + std::to_string(kn) + " kangaroos at their offsets", ts);
+            ok = rc == 0;
+            if (ok && e == 0) {
+                ts = Clock::now();
+                uint64_t entry = 0;
+                const int rt = table_check(dev, mode, p.check_table, &entry);
+                if (rt < 0) bad("bsgs_kangaroo_verify_points");
+                else if (rt) end_with("Recovery file is damaged: table entry " + std::to_string(entry) + " does not match its offset");
+                else verified("", "table: " + std::to_string(p.check_table.size() / 32) + " entries", ts);
+                ok = rt == 0;
+                std::vector<uint8_t>().swap(p.check_table);
+            }
+        }
+        sh.checked++;
+        while (sh.checked.load() < p.pl.engines && !sh.stop.load()) std::this_thread::sleep_for(std::chrono::milliseconds(1));
+    }
+    bool first_launch = true;
     std::vector<bsgs_kangaroo_record> recs(ok ? p.pl.cap : 0);
     while (ok) {
         if (!sh.stop.load()) {
@@ -171,11 +254,21 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
             { std::lock_guard<std::mutex> lk(sh.q_m); sh.queue.emplace_back(e, std::vector<bsgs_kangaroo_record>(recs.begin(), recs.begin() + n)); }
             sh.q_cv.notify_one();
             if (c.ksteps && total >= c.ksteps) sh.stop = true;
+            if (first_launch && e == 0) test_corrupt_kangaroo(dev, kn);  // (test build only)
+            first_launch = false;
         }
         // the herd as it stands leaves the device between two launches when a save is requested, and at the end when the search is not done (the last save)
         const bool stopped = sh.stop.load();
         bool want = sh.save_req.load();
         if (stopped) { std::lock_guard<std::mutex> lt(sh.tab_m); want = !mode.done(); }
+        if (want && check && !sh.failed.load()) {                      // before every save: a herd that went wrong never replaces a good file
+            const auto ts = Clock::now();
+            uint32_t at = 0;
+            const int rc = herd_check(dev, mode, kn, &at);
+            if (rc < 0) { bad("bsgs_kangaroo_verify"); break; }
+            if (rc) { end_with("herd of engine " + std::to_string(e) + " failed verification at kangaroo " + std::to_string(at) + ": kangaroo.work left as it was"); break; }
+            if (stopped) verified("\n", "herd " + std::to_string(e) + ": " + std::to_string(kn) + " kangaroos at their offsets", ts);      // (the -wt saves stay silent)
+        }
         if (want) {
             sh.saved[e].resize(kn);
             if (bsgs_kangaroo_download(dev, 0, (uint32_t)kn, sh.saved[e].data()) != BSGS_OK) { bad("bsgs_kangaroo_download"); sh.saved[e].clear(); break; }
@@ -240,6 +333,7 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
     signal(SIGTERM, on_signal);
     // (engines are not started if the search ended while the mode prepared it: a start at infinity in the host's seeding is the key)
     std::vector<std::thread> th;
+    if (c.verify && mode.verify_skip && !sh.stop.load()) printf("[verify] skipped: %s\n", mode.verify_skip);
     sh.running = sh.stop.load() ? 0 : pl.engines;
     if (!sh.stop.load()) for (uint32_t e = 0; e < pl.engines; e++) th.emplace_back(engine, e, std::cref(c), std::ref(p), std::ref(sh), std::ref(mode));
     auto last_t = Clock::now(), last_save = Clock::now();

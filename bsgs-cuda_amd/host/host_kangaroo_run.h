@@ -20,6 +20,7 @@ struct Prologue {
     bool resume = false, go = true;
     std::string wl_path, work_path, work_tmp;
     WorkFile wf;                                   // -wl: header, key list, re-seed lists; the table until the mode has restored it
+    std::vector<uint8_t> check_table;              // -wl: the file's table entries as read, until the first engine has verified them
     std::vector<std::vector<bsgs_kangaroo_state>> herds;      // per engine, the herd to upload: the file's, or what a mode computed before the engines start
     double elapsed_before = 0.0;
     Clock::time_point t0 = Clock::now();           // what "Job time" counts from: each mode sets it where it always did
@@ -46,6 +47,8 @@ struct Shared {
     std::vector<std::vector<uint32_t>> reseed;     // per engine: kangaroos (local index) to start afresh
     std::vector<uint64_t> engine_records;
     std::mutex err_m; std::string err;
+    std::atomic<bool> failed{false};               // err is set
+    std::atomic<uint32_t> checked{0};              // -wl: engines whose herd (the first one: and the saved table) went through the verification; none walks before all have
     // saving ("a save is a consistent cut"): engines park between two launches with their herd downloaded
     std::atomic<bool> save_req{false};
     std::mutex save_m; std::condition_variable save_cv;
@@ -74,6 +77,11 @@ public:
     // under sh.tab_m.  One record of engine e into the table: kangaroos to start afresh go on sh's lists, a finished search sets sh.stop; false: the rest of
     // the batch is not looked at
     virtual bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &sh) = 0;
+    // what the verification needs (bsgs_kangaroo_verify, bsgs_kangaroo_verify_points; set in before_devices): the one Q of every wild kangaroo, or null: the
+    // key list the engines got in setup(); why the device cannot check this search, or null; the flags a table entry's type or owner word stands for
+    const uint8_t *verify_q = nullptr;
+    const char *verify_skip = nullptr;
+    virtual uint32_t entry_flags(uint32_t word) const = 0;
     virtual bool done() const = 0;
     virtual bool give_up(uint64_t steps) = 0;
     virtual void status(double rate, uint64_t steps, uint64_t dps) const = 0;

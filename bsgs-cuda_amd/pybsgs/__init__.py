@@ -28,7 +28,7 @@ NATIVE_SYMBOLS = [
     "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
     "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym",
-    "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_selftest_fe3",
+    "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_kangaroo_verify", "bsgs_kangaroo_verify_points", "bsgs_selftest_fe3",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc"]
@@ -186,6 +186,8 @@ def lib():
             "bsgs_kangaroo_geometry": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
             "bsgs_kangaroo_set_keys": [vp, u8p, C.c_uint32],
             "bsgs_kangaroo_seed_keys": [vp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+            "bsgs_kangaroo_verify": [vp, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32],
+            "bsgs_kangaroo_verify_points": [vp, u8p, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32],
             "bsgs_kangaroo_seed": [vp, u8p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         }
         for name, args in sig.items():
@@ -708,6 +710,27 @@ class Device:
         _chk(self.L.bsgs_kangaroo_seed_keys(self.h, (C.c_uint32 * n)(*idx) if idx is not None else None, first, n, d, (C.c_uint32 * n)(*flags),
                                             (C.c_uint32 * n)(*keys), C.byref(ninf), C.byref(first_inf)))
         return ninf.value, first_inf.value
+
+    def kangaroo_verify(self, q=None, first=0, n=None, max_bad=64):
+        """every kangaroo of [first, first + n) (n None: to the end of the herd) against sigma*Q + d*G on the GPU, the herd untouched; q = (x, y), or None:
+        the list of kangaroo_set_keys.  -> (how many fail, [at most max_bad of them, ascending])"""
+        if n is None:
+            t, g, _ = self.kangaroo_geometry()
+            n = t * g - first
+        nbad, idx = C.c_uint32(), (C.c_uint32 * max(1, max_bad))()
+        _chk(self.L.bsgs_kangaroo_verify(self.h, le32(q[0]) + le32(q[1]) if q is not None else None, first, n, C.byref(nbad), idx, max_bad))
+        return nbad.value, list(idx[:min(nbad.value, max_bad)])
+
+    def kangaroo_verify_points(self, q, offsets, flags, x_lo64, max_bad=64):
+        """entries (d = offsets[k], a signed integer; flags[k] as a state's: WILD, NEG, key bits) against x_lo64[k], the low 64 bits of x(sigma*Q + d*G);
+        needs a herd (kangaroo_setup).  -> (how many fail, [at most max_bad positions, ascending])"""
+        n = len(offsets)
+        assert len(flags) == n and len(x_lo64) == n
+        d = b"".join((v % (1 << 128)).to_bytes(16, "little") for v in offsets)
+        nbad, idx = C.c_uint32(), (C.c_uint32 * max(1, max_bad))()
+        _chk(self.L.bsgs_kangaroo_verify_points(self.h, le32(q[0]) + le32(q[1]) if q is not None else None, n, d, (C.c_uint32 * max(1, n))(*flags),
+                                                (C.c_uint64 * max(1, n))(*x_lo64), C.byref(nbad), idx, max_bad))
+        return nbad.value, list(idx[:min(nbad.value, max_bad)])
 
     def kangaroo_geometry(self):
         t, g, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
