@@ -28,6 +28,7 @@ struct bsgs_kangaroo {
     uint32_t seed_cap = 0;
     u32x4 *mark = nullptr;                 // bsgs_kangaroo_setup_sym: the cycle check's marks, [2][N]
     uint32_t R = 0;                        // bsgs_kangaroo_setup_sym: jump points of the symmetric walk (0: the plain walk)
+    u32 *key = nullptr;                    // bsgs_kangaroo_setup_sym_keys: the key of each kangaroo, [N], = flags + N (nullptr for every other herd)
     u32x4 *keys = nullptr;                 // bsgs_kangaroo_set_keys: n_keys affine points Q_k, x || y (64 bytes each)
     uint32_t n_keys = 0;
     u32x4 *verify_q = nullptr;             // bsgs_kangaroo_verify*: the call's one Q, x || y (64 bytes)
@@ -153,6 +154,7 @@ static inline size_t bsgs_hitbuf_bytes(const bsgs_dev *d) { return 64 + (size_t)
 static inline void bsgs_le_to_fe(fe &f, const uint8_t *le) { memcpy(f.v, le, 32); }
 uint64_t bsgs_ovf_slots(uint64_t entries);                   // size of the overflow hash set for `entries` keys (power of two, load <= 1/2)
 int bsgs_ovf_fill(bsgs_dev *d, const u64 *list, uint64_t n, u64 *table, uint64_t slots);   // table := hash set of list[0..n)
+int bsgs_kangaroo_split_keys(bsgs_dev *d, const u32 *idx_dev, uint32_t first, uint32_t n);      // kangaroo.hip: flags WILD | key << 8 of the kangaroos just seeded -> flags, key[]
 void bsgs_kangaroo_release(bsgs_dev *d);                     // kangaroo.hip: frees the herd (bsgs_dev_close, a new bsgs_kangaroo_setup)
 // hand a finished "lines + overflow list" table to the engine (it becomes the owner of both buffers)
 int bsgs_install_lines(bsgs_dev *d, u32x4 *lines, int lplog, u64 *ovf, uint64_t ovf_n, uint64_t ht_items, uint64_t w,

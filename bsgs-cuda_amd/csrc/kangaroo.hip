@@ -28,9 +28,11 @@ __device__ __forceinline__ void lds_fe(fe &r, const char *q)
     r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w; r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
 }
 
-// one record per lane with `hit`: vector stores, one atomic per wave (as report() in giant_kernel.hip.h); slots past the capacity are counted, not written
+// one record per lane with `hit`: vector stores, one atomic per wave (as report() in giant_kernel.hip.h); slots past the capacity are counted, not written.
+// key: the per-kangaroo key array of a bsgs_kangaroo_setup_sym_keys herd, read here and nowhere else in the walk -- only by a lane that writes a record --
+// into the record's fourth word; nullptr (a constant at every other call site): the word is 0
 template <class ARGS>
-__device__ __forceinline__ void kang_record(const ARGS &A, bool hit, const fe &x, const u32x4 &d, u32 idx, u32 flags, u32 step, u32 lane)
+__device__ __forceinline__ void kang_record(const ARGS &A, bool hit, const fe &x, const u32x4 &d, u32 idx, u32 flags, u32 step, u32 lane, const u32 *key = nullptr)
 {
     const u64 m = __ballot(hit);
     if (m) {
@@ -44,7 +46,7 @@ __device__ __forceinline__ void kang_record(const ARGS &A, bool hit, const fe &x
             r[0] = (u32x4){x.v[0], x.v[1], x.v[2], x.v[3]};
             r[1] = (u32x4){x.v[4], x.v[5], x.v[6], x.v[7]};
             r[2] = d;
-            r[3] = (u32x4){idx, flags, step, 0u};
+            r[3] = (u32x4){idx, flags, step, key ? key[idx] : 0u};
         }
     }
 }
@@ -163,7 +165,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
 
 struct KangSymArgs {
     u32x4 *st;             // as KangArgs
-    u32 *flags;            // [N]: BSGS_KANGAROO_WILD | NEG | CYCLE | DEAD, last jump index (bit 8 valid, bits 9..20)
+    u32 *flags;            // [N]: BSGS_KANGAROO_WILD | NEG | CYCLE | DEAD, last jump index (bit 8 valid, bits 9..20); kangaroo_sym_keys_kernel: then key[N]
     u32x4 *chain;
     const u32x4 *table;    // {x, y}[R] (64 bytes each), then s[R]
     u32 *rec;
@@ -205,8 +207,10 @@ __device__ __forceinline__ u32 kang_sym_element(fe &e, const fe &x, const fe &jx
     return 2u;
 }
 
-template <bool BLOCK_INV>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) kangaroo_sym_kernel(const KangSymArgs A)
+// the symmetric step, shared by the two entry points below.  KEYS: the herd of bsgs_kangaroo_setup_sym_keys, whose key array lies behind the flags
+// (flags[N + i]: no pointer of its own, the walk has no scalar register to spare for one); see kang_record
+template <bool BLOCK_INV, bool KEYS>
+__device__ __forceinline__ void kang_sym_walk(const KangSymArgs &A)
 {
     const u32 T = A.T, N = A.N, G = A.G, rmask = A.rmask;
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;             // the launch has exactly T threads
@@ -299,13 +303,27 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                 A.flags[i] = fl;
                 rec = true;
             }
-            kang_record(A, rec, x, d, i, fl, step, lane);
+            kang_record(A, rec, x, d, i, fl, step, lane, KEYS ? A.flags + N : nullptr);
         }
     }
 }
 
+template <bool BLOCK_INV>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) kangaroo_sym_kernel(const KangSymArgs A)
+{
+    kang_sym_walk<BLOCK_INV, false>(A);
+}
+
+// the herd of bsgs_kangaroo_setup_sym_keys (include/bsgs_hip.h, "Kangaroo, many keys, symmetric walk"): the same step; a record names its kangaroo's key
+template <bool BLOCK_INV>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) kangaroo_sym_keys_kernel(const KangSymArgs A)      // flags: [2][N], flags | key
+{
+    kang_sym_walk<BLOCK_INV, true>(A);
+}
+
 // ---- gather / scatter of whole states (host format bsgs_kangaroo_state, 96 bytes) -------------------------------------------------------------------
-__global__ void kangaroo_scatter_kernel(u32x4 *st, u32 *flags, u32 N, const u32x4 *in, const u32 *idx, u32 first, u32 n)
+// key: the key array of a bsgs_kangaroo_setup_sym_keys herd (state word reserved[0]), or nullptr: the word is ignored on upload and 0 on download
+__global__ void kangaroo_scatter_kernel(u32x4 *st, u32 *flags, u32 *key, u32 N, const u32x4 *in, const u32 *idx, u32 first, u32 n)
 {
     const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -314,15 +332,34 @@ __global__ void kangaroo_scatter_kernel(u32x4 *st, u32 *flags, u32 N, const u32x
     const u32x4 *s = in + (u64)k * 6;
     for (u32 f = 0; f < 5; f++) st[(u64)f * N + i] = s[f];
     flags[i] = s[5].x;
+    if (key) key[i] = s[5].y;
 }
-__global__ void kangaroo_gather_kernel(const u32x4 *st, const u32 *flags, u32 N, u32x4 *out, u32 first, u32 n)
+__global__ void kangaroo_gather_kernel(const u32x4 *st, const u32 *flags, const u32 *key, u32 N, u32x4 *out, u32 first, u32 n)
 {
     const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const u32 i = first + k;
     u32x4 *o = out + (u64)k * 6;
     for (u32 f = 0; f < 5; f++) o[f] = st[(u64)f * N + i];
-    o[5] = (u32x4){flags[i], 0u, 0u, 0u};
+    o[5] = (u32x4){flags[i], key ? key[i] : 0u, 0u, 0u};
+}
+// after kangaroo_seed_keys_kernel on a bsgs_kangaroo_setup_sym_keys herd: the seeded kangaroos' key leaves the flags, where the walk keeps its last jump index
+__global__ void kangaroo_split_keys_kernel(u32 *flags, u32 *key, u32 N, const u32 *idx, u32 first, u32 n)
+{
+    const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const u32 i = idx ? idx[k] : first + k;
+    if (i >= N) return;
+    const u32 fl = flags[i];
+    key[i] = (fl >> BSGS_KANGAROO_KEY_SHIFT) & 0xFFFFu;
+    flags[i] = fl & (BSGS_KANGAROO_WILD | BSGS_KANGAROO_DEAD);
+}
+int bsgs_kangaroo_split_keys(bsgs_dev *d, const u32 *idx_dev, uint32_t first, uint32_t n)
+{
+    bsgs_kangaroo *k = d->kangaroo;
+    hipLaunchKernelGGL(kangaroo_split_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, d->stream, k->flags, k->key, k->N, idx_dev, first, n);
+    HIPCHK(hipGetLastError());
+    return BSGS_OK;
 }
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
@@ -343,7 +380,7 @@ static_assert(sizeof(bsgs_kangaroo_record) == 64, "DP record: 64 bytes");
 
 // the herd of both walks; n_jumps = 0: the plain walk's 64 points in its LDS layout x[64] | y[64] | s[64]; else the symmetric walk's {x, y}[R] | s[R]
 static int kangaroo_alloc(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t n_jumps, uint32_t dp, uint32_t herd, uint32_t per_thread,
-                          uint32_t record_cap)
+                          uint32_t record_cap, bool keyed = false)
 {
     const uint32_t R = n_jumps ? n_jumps : KANG_NJ;
     if (!d || !jumps_xy_le || !jump_scalars) return fail(BSGS_ERR_ARG, "null");
@@ -359,7 +396,8 @@ static int kangaroo_alloc(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_
     k->N = herd; k->G = per_thread; k->T = herd / per_thread; k->dp = dp; k->cap = record_cap; k->R = n_jumps;
     k->block = k->T % 256u == 0 ? 256u : 64u;
     HIPCHK(hipMalloc(&k->st, (size_t)herd * 5 * 16));
-    HIPCHK(hipMalloc(&k->flags, (size_t)herd * 4));
+    HIPCHK(hipMalloc(&k->flags, (size_t)herd * (keyed ? 8 : 4)));
+    if (keyed) k->key = k->flags + herd;                                         // (the walk finds the keys behind the flags)
     HIPCHK(hipMalloc(&k->chain, (size_t)herd * 32));
     HIPCHK(hipMalloc(&k->table, (size_t)R * 72));
     if (n_jumps) HIPCHK(hipMalloc(&k->mark, (size_t)herd * 32));
@@ -368,6 +406,7 @@ static int kangaroo_alloc(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_
     HIPCHK(hipMemsetAsync(k->st, 0, (size_t)herd * 5 * 16, d->stream));
     HIPCHK(hipMemsetAsync(k->flags, 0xFF, (size_t)herd * 4, d->stream));         // every kangaroo dead until its state is uploaded
     if (n_jumps) HIPCHK(hipMemsetAsync(k->mark, 0, (size_t)herd * 32, d->stream));
+    if (keyed) HIPCHK(hipMemsetAsync(k->key, 0, (size_t)herd * 4, d->stream));
     std::vector<uint8_t> tab((size_t)R * 72);
     for (uint32_t j = 0; j < R; j++) {
         if (n_jumps) memcpy(&tab[j * 64], jumps_xy_le + j * 64, 64);
@@ -393,6 +432,13 @@ extern "C" int bsgs_kangaroo_setup_sym(bsgs_dev *d, const uint8_t *jumps_xy_le, 
         return fail(BSGS_ERR_ARG, "%u jump points: a power of two, 64..%u", n_jumps, BSGS_KANGAROO_SYM_MAX_JUMPS);
     return kangaroo_alloc(d, jumps_xy_le, jump_scalars, n_jumps, dp, herd, per_thread, record_cap);
 }
+extern "C" int bsgs_kangaroo_setup_sym_keys(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t n_jumps, uint32_t dp, uint32_t herd,
+                                            uint32_t per_thread, uint32_t record_cap)
+{
+    if (n_jumps < 64u || n_jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (n_jumps & (n_jumps - 1u)))
+        return fail(BSGS_ERR_ARG, "%u jump points: a power of two, 64..%u", n_jumps, BSGS_KANGAROO_SYM_MAX_JUMPS);
+    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, n_jumps, dp, herd, per_thread, record_cap, true);
+}
 
 static int kangaroo_put(bsgs_dev *d, const uint32_t *idx, uint32_t first, uint32_t n, const bsgs_kangaroo_state *states)
 {
@@ -413,7 +459,7 @@ static int kangaroo_put(bsgs_dev *d, const uint32_t *idx, uint32_t first, uint32
     }
     HIPCHK(hipMemcpyAsync(k->staging, states, (size_t)n * 96, hipMemcpyHostToDevice, d->stream));
     if (idx) HIPCHK(hipMemcpyAsync(k->idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, d->stream));
-    hipLaunchKernelGGL(kangaroo_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, d->stream, k->st, k->flags, k->N, k->staging, idx ? k->idx : nullptr, first, n);
+    hipLaunchKernelGGL(kangaroo_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, d->stream, k->st, k->flags, k->key, k->N, k->staging, idx ? k->idx : nullptr, first, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(d->stream));
     return BSGS_OK;
@@ -438,7 +484,7 @@ extern "C" int bsgs_kangaroo_download(bsgs_dev *d, uint32_t first, uint32_t n, b
     HIPCHK(hipSetDevice(d->id));
     u32x4 *out = nullptr;
     HIPCHK(hipMalloc(&out, (size_t)n * 96));
-    hipLaunchKernelGGL(kangaroo_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, d->stream, k->st, k->flags, k->N, out, first, n);
+    hipLaunchKernelGGL(kangaroo_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, d->stream, k->st, k->flags, k->key, k->N, out, first, n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(states, out, (size_t)n * 96, hipMemcpyDeviceToHost, d->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
@@ -464,7 +510,10 @@ extern "C" int bsgs_kangaroo_run(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_reco
         S.st = k->st; S.flags = k->flags; S.chain = k->chain; S.table = k->table; S.rec = k->rec; S.mark = k->mark;
         S.N = k->N; S.T = k->T; S.G = k->G; S.steps = steps; S.dp_mask = A.dp_mask; S.cap = k->cap; S.rmask = k->R - 1u;
         S.mark_step = steps > BSGS_KANGAROO_CYCLE_WINDOW ? steps - 1u - BSGS_KANGAROO_CYCLE_WINDOW : ~0u;
-        if (k->block == 256u) hipLaunchKernelGGL(kangaroo_sym_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_TABLE_OFF, d->stream, S);
+        if (k->key) {
+            if (k->block == 256u) hipLaunchKernelGGL(kangaroo_sym_keys_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_TABLE_OFF, d->stream, S);
+            else hipLaunchKernelGGL(kangaroo_sym_keys_kernel<false>, dim3(k->T / 64u), dim3(64), 0, d->stream, S);
+        } else if (k->block == 256u) hipLaunchKernelGGL(kangaroo_sym_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_TABLE_OFF, d->stream, S);
         else hipLaunchKernelGGL(kangaroo_sym_kernel<false>, dim3(k->T / 64u), dim3(64), 0, d->stream, S);
     } else if (k->block == 256u) hipLaunchKernelGGL(kangaroo_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_LDS, d->stream, A);
     else hipLaunchKernelGGL(kangaroo_kernel<false>, dim3(k->T / 64u), dim3(64), KANG_LDS, d->stream, A);

@@ -101,7 +101,10 @@ __global__ void __launch_bounds__(256) kangaroo_seed_keys_kernel(const KeySeedAr
         } else zi = inv;
         const u32 i = A.idx ? A.idx[k] : A.first + k;
         if (i >= N) continue;                                        // (the host has checked: never taken)
-        const u32 fl = A.fl[k];                                      // the key index stays in the kangaroo's flags: the walk copies the word into every record
+        // the key index stays in the kangaroo's flags: the plain walk copies the word into every record.  A herd of bsgs_kangaroo_setup_sym_keys holds the
+        // word only until kangaroo_split_keys_kernel, queued behind this launch on the same stream, has moved the key to the key array: no walk runs between
+        // the two, so the symmetric step never takes key bits for its last jump index
+        const u32 fl = A.fl[k];
         sd[i] = A.d[k];
         if (__builtin_expect((infinite >> b) & 1u, 0)) {
             const u32x4 zero = {0u, 0u, 0u, 0u};
@@ -132,7 +135,7 @@ extern "C" int bsgs_kangaroo_set_keys(bsgs_dev *d, const uint8_t *q_xy_le, uint3
     if (!d || !q_xy_le) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = d->kangaroo;
     if (!k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
-    if (k->R) return fail(BSGS_ERR_STATE, "a herd of the symmetric walk takes one key (its flags hold the last jump index where the key index would go)");
+    if (k->R && !k->key) return fail(BSGS_ERR_STATE, "a herd of the symmetric walk takes one key (its flags hold the last jump index where the key index would go; bsgs_kangaroo_setup_sym_keys makes one that takes a list)");
     if (!n_keys || n_keys > BSGS_KANGAROO_MAX_KEYS) return fail(BSGS_ERR_ARG, "%u keys: 1..%u", n_keys, BSGS_KANGAROO_MAX_KEYS);
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -151,7 +154,7 @@ extern "C" int bsgs_kangaroo_seed_keys(bsgs_dev *d, const uint32_t *idx, uint32_
     if (!d || !d_le || !flags || !key) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = d->kangaroo;
     if (!k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
-    if (k->R) return fail(BSGS_ERR_STATE, "a herd of the symmetric walk takes one key");
+    if (k->R && !k->key) return fail(BSGS_ERR_STATE, "a herd of the symmetric walk takes one key");
     if (n_infinite) *n_infinite = 0;
     if (first_infinite) *first_infinite = 0;
     if (!n) return BSGS_OK;
@@ -186,6 +189,8 @@ extern "C" int bsgs_kangaroo_seed_keys(bsgs_dev *d, const uint32_t *idx, uint32_
         A.TT = ((m + A.B - 1) / A.B + 255u) / 256u * 256u;
         hipLaunchKernelGGL(kangaroo_seed_keys_kernel, dim3(A.TT / 256u), dim3(256), SEED_LDS, d->stream, A);
         HIPCHK(hipGetLastError());
+        // a herd of bsgs_kangaroo_setup_sym_keys: the key moves from the stored word to the key array (this kernel sits at its register budget: a pass of its own)
+        if (k->key) if (int rc = bsgs_kangaroo_split_keys(d, A.idx, A.first, m)) return rc;
     }
     uint32_t out[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(out, k->seed_out, 8, hipMemcpyDeviceToHost, d->stream));

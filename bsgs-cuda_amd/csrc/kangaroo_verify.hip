@@ -12,6 +12,7 @@
 struct VerifyArgs {
     const u32x4 *st;       // [5][N]: x.lo, x.hi, y.lo, y.hi, d (herd in place)
     const u32 *flags;      // [N]
+    const u32 *key;        // [N]: the keys of a bsgs_kangaroo_setup_sym_keys herd checked against its list (its flags hold no key), else nullptr
     const u32x4 *comb;     // [16][255] points, x || y
     const u32x4 *q;        // [nq] points Q_k, x || y: the call's one Q (nq = 1, key_mask = 0) or the herd's key list
     const u32x4 *d;        // [n] staged offsets, two's complement (points of a list)
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(256) kangaroo_verify_kernel(const VerifyArgs A
         const u32 fl = A.flags[i];
         const u32x4 dv = A.st[4 * (u64)N + i];
         const bool wild = (fl & BSGS_KANGAROO_WILD) != 0u;
-        const u32 key = (fl >> BSGS_KANGAROO_KEY_SHIFT) & A.key_mask; // 0 with the call's one Q: a symmetric herd keeps its last jump index in these bits
+        const u32 key = A.key ? A.key[i] : (fl >> BSGS_KANGAROO_KEY_SHIFT) & A.key_mask;      // 0 with the call's one Q: a symmetric herd keeps its last jump index in these bits
         if (wild ? key >= A.nq : (key != 0u || (fl & BSGS_KANGAROO_NEG) != 0u)) bad = true;       // a key beyond the list (nothing is read for it), a tame
                                                                                                   // kangaroo with a key or with NEG: the state is wrong
         else {
@@ -168,6 +169,7 @@ static int verify_begin(bsgs_dev *d, bsgs_kangaroo *k, const uint8_t *q_xy_le, u
     A.q = q_xy_le ? k->verify_q : k->keys;
     A.nq = q_xy_le ? 1u : k->n_keys;
     A.key_mask = q_xy_le ? 0u : 0xFFFFu;
+    A.key = q_xy_le ? nullptr : k->key;
     return BSGS_OK;
 }
 // the count and what the list holds of it, ascending (launches of one stream fill the list in their order: the lowest-numbered chunk's failures come first)

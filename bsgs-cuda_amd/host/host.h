@@ -235,4 +235,6 @@ int kangaroo_roundtrip_selftest(const std::vector<std::string> &args);
 int kangaroo_sym_selftest(const std::vector<std::string> &args);                 // -selftest kangaroo-sym: the symmetric walk's table
 int kangaroo_sym_roundtrip_selftest(const std::vector<std::string> &args);       // -selftest kangaroo-sym-roundtrip: through a version-2 work file
 int kangaroo_multi_roundtrip_selftest(const std::vector<std::string> &args);     // -selftest kangaroo-multi-roundtrip: through a version-3 work file
+int kangaroo_symlist_selftest(const std::vector<std::string> &args);             // -selftest kangaroo-symlist: the table of -infile -kwalk sym (host_kangaroo_symlist.cpp)
+int kangaroo_symlist_roundtrip_selftest(const std::vector<std::string> &args);   // -selftest kangaroo-symlist-roundtrip: through a version-4 work file
 int kangaroo_multi_selftest(const std::vector<std::string> &args);               // -selftest kangaroo-multi: the table for a list of keys (host_kangaroo_multi.cpp)

@@ -69,6 +69,7 @@ void usage(const Config &c)
            c.t, c.b, c.p, c.pk.c_str(), c.htsz, c.wt);
     printf("-kangaroo    Pollard's kangaroo search of a public key (-pb), or of every key of a list (-infile) with one herd, in [-pk, -pke], 2^20 <= width <= 2^125, no baby table; with -d, -dir, -wl, -wt (not with -w -htsz -onlygen;\n"
            "             -infile: not with -pb, -ksym; saved as kangaroo.work version 3, which only -infile -wl continues)\n"
+           "-kwalk W     Kangaroo: plain (default) or sym, the symmetric walk (negation map): with -pb the same as -ksym, with -infile the list search with that walk (kangaroo.work version 4)\n"
            "-dp N        Kangaroo: distinguished points have the top N bits of x zero (0..32; default chosen from the range)\n"
            "-kn N        Kangaroo: kangaroos per engine (default chosen from the range)\n"
            "-kseed S     Kangaroo: seed of the herds and the jump table (default: random, printed)\n"

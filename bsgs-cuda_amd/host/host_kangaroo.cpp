@@ -13,13 +13,6 @@
 using namespace kang;
 namespace {
 
-// -ksym (tests/kangaroo_sym_model.py herd_offset): tame uniform in [0, W/2), wild uniform in [-W/4, W/4), the same stream
-i128 herd_offset_sym(uint64_t &state, u128 W, bool wild)
-{
-    u128 r = draw128(state) % (W / 2);
-    while (!wild && !r) r = draw128(state) % (W / 2);                 // a tame kangaroo at 0 would stand on the point at infinity: the next draw
-    return wild ? (i128)r - (i128)(W / 4) : (i128)r;
-}
 // v / 2 mod n
 Scalar sc_half(Scalar v)
 {
@@ -254,6 +247,7 @@ const double KSYM_JUMPSCALE = 2.0;                 // DESIGN.md 10, "jump scale"
 KangConfig kang::parse_kangaroo_args(int argc, char **argv)
 {
     KangConfig c;
+    bool ksym = false, kwalk_sym = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         for (auto &ch : a) ch = (char)tolower(ch);
@@ -273,17 +267,21 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-wt") c.wt = std::max(30, atoi(next().c_str()));
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
-        else if (a == "-ksym") c.sym = true;
+        else if (a == "-ksym") ksym = true;
+        else if (a == "-kwalk") { const std::string w = next(); if (w != "plain" && w != "sym") die("-kwalk must be plain or sym"); kwalk_sym = w == "sym"; }
         else if (a == "-noverify") c.verify = false;
         else if (a == "-kjumps") { c.jumps = (uint32_t)strtoul(next().c_str(), nullptr, 10); if (c.jumps < 64 || c.jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (c.jumps & (c.jumps - 1))) die("-kjumps must be a power of two, 64..4096"); }
         else if (a == "-kjumpscale") { c.jumpscale = atof(next().c_str()); if (!(c.jumpscale >= 1.0 / 64 && c.jumpscale <= 64.0)) die("-kjumpscale must be 1/64..64"); }
         else if (a == "-w" || a == "-htsz" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table)");
         else die("Unknown parameter with -kangaroo: " + a);
     }
-    if (!c.sym && (c.jumps || c.jumpscale != 0.0)) die("-kjumps and -kjumpscale belong to -ksym");
+    // -kwalk sym: the symmetric walk of whatever is searched -- one key (-pb; the same as -ksym) or the list of -infile
+    c.symlist = kwalk_sym && !c.infile.empty();
+    c.sym = ksym || (kwalk_sym && c.infile.empty());
+    if (!c.sym && !c.symlist && (c.jumps || c.jumpscale != 0.0)) die("-kjumps and -kjumpscale belong to -ksym");
     if (!c.infile.empty()) {
         if (c.pub_given) die("-kangaroo: -pb and -infile exclude each other (the keys come from the file)");
-        if (c.sym) die("-kangaroo -ksym cannot be combined with -infile: the symmetric walk keeps its last jump index in the flag bits that carry the key of a wild kangaroo, and its collision rule across keys is not built");
+        if (ksym) die("-kangaroo -ksym cannot be combined with -infile: -ksym is the symmetric walk for one key (-kwalk sym searches a list with the symmetric walk)");
     }
     return c;
 }
@@ -466,7 +464,7 @@ int kangaroo_main(int argc, char **argv)
 {
     printf("BSGS MI355X kangaroo mode on %s\n", bsgs_version());
     const KangConfig c = parse_kangaroo_args(argc, argv);
-    if (!c.infile.empty()) return kangaroo_multi_main(c);
+    if (!c.infile.empty()) return c.symlist ? kangaroo_symlist_main(c) : kangaroo_multi_main(c);
     Affine P;
     if (!hs::parse_pubkey(P, c.pub) || !hs::on_curve(P)) die("Invalid Public Key (-pb) length!!!");
     Prologue p(c);

@@ -24,6 +24,13 @@ inline i128 herd_offset(uint64_t &state, u128 W, bool wild)
     const u128 r = draw128(state);
     return wild ? (i128)(r % W) - (i128)(W / 2) : (i128)(1 + r % (W - 1));
 }
+// the symmetric walk (tests/kangaroo_sym_model.py herd_offset): tame uniform in [0, W/2), wild uniform in [-W/4, W/4), the same stream
+inline i128 herd_offset_sym(uint64_t &state, u128 W, bool wild)
+{
+    u128 r = draw128(state) % (W / 2);
+    while (!wild && !r) r = draw128(state) % (W / 2);                 // a tame kangaroo at 0 would stand on the point at infinity: the next draw
+    return wild ? (i128)r - (i128)(W / 4) : (i128)r;
+}
 inline Scalar sc_from_i128(i128 v) { return v >= 0 ? hs::sc_from_u128((u128)v) : hs::sc_neg(hs::sc_from_u128((u128)-v)); }
 
 // fixed-base comb for 128-bit scalars: table[k][v] = v * 2^(8k) * G, sixteen mixed additions per point
@@ -60,7 +67,8 @@ struct KangConfig {
     bool cpuseed = false;                          // -kcpuseed: start points from the host's comb instead of bsgs_kangaroo_seed
     std::string infile;                            // -infile: a list of public keys in the one range (host_kangaroo_multi.cpp)
     bool pub_given = false;
-    bool sym = false;                              // -ksym: the symmetric walk (negation map)
+    bool sym = false;                              // -ksym, or -kwalk sym with -pb: the symmetric walk (negation map)
+    bool symlist = false;                          // -kwalk sym with -infile: the symmetric walk for the key list (host_kangaroo_symlist.cpp)
     uint32_t jumps = 0;                            // -kjumps: jump points of the symmetric walk (default 1024; resumed: from the work file)
     double jumpscale = 0.0;                        // -kjumpscale: mean jump = scale * N_k sqrt(W) / 4 (default KSYM_JUMPSCALE; resumed: from the work file)
     bool verify = true;                            // -noverify: herds and the saved table are not checked against their offsets (at -wl, before every save)
@@ -72,8 +80,9 @@ struct Plan { uint32_t engines, dp, G, S, cap; uint64_t kn; double expected; };
 // thread at four waves per SIMD; dp_arg < 0 / kn_arg == 0: chosen here.  S and cap are left to the caller (they depend on the expected total).
 Plan plan_herd(double sqrtW, uint32_t engines, int cus, int dp_arg, uint64_t kn_arg);
 
-// ---- the work file <dir>/kangaroo.work: version 1 the plain walk, 2 -ksym, 3 a list of keys (-infile) ------------------------------
+// ---- the work file <dir>/kangaroo.work: version 1 the plain walk, 2 -ksym, 3 a list of keys (-infile), 4 a list with -kwalk sym --------
 const uint32_t WORK_VERSION = 1, WORK_VERSION_SYM = 2, WORK_VERSION_KEYS = 3;       // 2: written and read by -ksym only; the header continues behind the fingerprint
+const uint32_t WORK_VERSION_SYMKEYS = 4;           // the layout of 3 with the header fields of 2 behind the fingerprint, links of 48 bytes, NEG in bit 31 of an owner word
 struct WorkHeader {
     uint32_t version = WORK_VERSION, jumps = 0;
     double jumpscale = 0.0;
@@ -83,8 +92,9 @@ struct WorkHeader {
     double elapsed = 0.0;
     std::string fingerprint;                       // 40 hex digits
 };
-struct WorkLink { uint32_t j, k; i128 delta; };                  // k_j = k_k + delta
-// version 3, between header and table: per key a status byte (1 solved) and the key when solved, the link counters, the open links
+// version 3: k_j = k_k + delta.  Version 4: sigma1 k''_j + d1 = +-(sigma2 k''_k + d2), sigma = +-1 (delta unused)
+struct WorkLink { uint32_t j, k; i128 delta; int32_t s1 = 0, s2 = 0; i128 d1 = 0, d2 = 0; };
+// versions 3 and 4, between header and table: per key a status byte (1 solved) and the key when solved, the link counters, the open links
 struct WorkKeys { std::vector<uint8_t> solved; std::vector<Scalar> key; std::vector<WorkLink> links; uint64_t kept = 0, resolved = 0; };
 struct WorkFile {
     WorkHeader h;
@@ -99,7 +109,7 @@ bool write_work(const std::string &dst, const std::string &tmp, const WorkHeader
 // "" when the file is a complete work file of version `want` (0: of any version), else what is wrong with it; with_body = false reads the header and checks
 // the sections' sizes only
 std::string read_work(const std::string &path, WorkFile &w, bool with_body, uint32_t want);
-// SHA-1 over what a resumed run must share with the run that saved: one key (versions 1 and 2), a list (version 3)
+// SHA-1 over what a resumed run must share with the run that saved: one key (versions 1 and 2), a list (versions 3 and 4)
 std::string kangaroo_fingerprint(const Affine &P, const Scalar &lo, const Scalar &hi, const WorkHeader &h);
 std::string keys_fingerprint(const std::vector<Affine> &P, const Scalar &lo, const Scalar &hi, const WorkHeader &h);
 
@@ -112,3 +122,4 @@ std::vector<std::string> split_commas(const std::string &rec);
 }  // namespace kang
 
 int kangaroo_multi_main(const kang::KangConfig &c);      // host_kangaroo_multi.cpp: -kangaroo -infile
+int kangaroo_symlist_main(const kang::KangConfig &c);    // host_kangaroo_symlist.cpp: -kangaroo -infile -kwalk sym

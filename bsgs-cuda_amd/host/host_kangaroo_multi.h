@@ -1,8 +1,10 @@
 // host_kangaroo_multi.h -- MultiKeyTable: the table of distinguished points of kangaroo mode for a list of public keys in one range
-// (host_kangaroo_multi.cpp; the rule: include/bsgs_hip.h "Kangaroo, many keys").
+// (host_kangaroo_multi.cpp; the rule: include/bsgs_hip.h "Kangaroo, many keys"), and Assigner, which the list search of either walk shares out its wild
+// kangaroos with (host_kangaroo_symlist.cpp is the other).
 #pragma once
 #include "host_kangaroo.h"
 
+#include <set>
 #include <unordered_map>
 
 class MultiKeyTable {
@@ -47,3 +49,43 @@ private:
     uint64_t false_ = 0, reseeds_ = 0, kept_ = 0, resolved_ = 0, live_links_ = 0;
     uint32_t solved_ = 0;
 };
+
+// which key a wild kangaroo works on (include/bsgs_hip.h "Kangaroo, many keys", assignment; tests/kangaroo_multi_model.py Assigner)
+class Assigner {
+public:
+    Assigner(uint32_t L, const std::vector<bool> &presolved, uint64_t n_wild) : count_(L, 0), key_(n_wild)
+    {
+        for (uint32_t k = 0; k < L; k++) if (!presolved[k]) open_.push_back(k);
+        for (uint64_t w = 0; w < n_wild; w++) { key_[w] = open_[w % open_.size()]; count_[key_[w]]++; }
+        for (uint32_t k : open_) by_count_.insert({count_[k], k});
+    }
+    uint32_t key(uint64_t w) const { return key_[w]; }
+    void solved(uint32_t k) { by_count_.erase({count_[k], k}); }                   // k takes no kangaroo from now on
+    // the key of wild kangaroo w from now on: its own while that is open, else the open key with the fewest kangaroos, lowest position first; false: none open
+    template <class TABLE> bool reseed(uint64_t w, const TABLE &t, uint32_t *k)
+    {
+        const uint32_t old = key_[w];
+        if (!t.known(old)) { *k = old; return true; }
+        if (by_count_.empty()) return false;
+        const uint32_t best = by_count_.begin()->second;
+        by_count_.erase(by_count_.begin());
+        count_[old]--; count_[best]++;
+        by_count_.insert({count_[best], best});
+        key_[w] = best; *k = best;
+        return true;
+    }
+    const std::vector<uint32_t> &keys() const { return key_; }
+    // -wl: every wild kangaroo's key as its saved state names it
+    template <class TABLE> void restore(const std::vector<uint32_t> &keys, const TABLE &t)
+    {
+        key_ = keys;
+        std::fill(count_.begin(), count_.end(), 0u);
+        for (uint32_t k : key_) count_[k]++;
+        by_count_.clear();
+        for (uint32_t k : open_) if (!t.known(k)) by_count_.insert({count_[k], k});
+    }
+private:
+    std::vector<uint32_t> open_, count_, key_;
+    std::set<std::pair<uint32_t, uint32_t>> by_count_;                             // (kangaroos, list position) of the keys still open
+};
+

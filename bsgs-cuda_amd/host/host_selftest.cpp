@@ -143,6 +143,10 @@ int selftest(int argc, char **argv)
             return kangaroo_sym_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-sym-roundtrip") {
             return kangaroo_sym_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-symlist-roundtrip") {                  // the table of -infile -kwalk sym through a version-4 work file
+            return kangaroo_symlist_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-symlist") {                            // the same table on a scripted record stream (host_kangaroo_symlist.cpp)
+            return kangaroo_symlist_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-multi-roundtrip") {                    // the same through a version-3 work file in the middle of the stream
             return kangaroo_multi_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-multi") {                              // the table for a list of keys on a scripted record stream (host_kangaroo_multi.cpp)

@@ -27,7 +27,7 @@ NATIVE_SYMBOLS = [
     "bsgs_tiles_per_launch", "bsgs_engine_geometry", "bsgs_run_digest", "bsgs_selftest_lo64", "bsgs_compat_stats", "bsgs_debug_buffers", "bsgs_alloc_stats", "bsgs_tune_placement", "bsgs_chain_placement", "bsgs_chain_grades", "bsgs_debug_grade_rule", "bsgs_debug_xcd_profile",
     "bsgs_table_checksum", "bsgs_sample_g2", "bsgs_alloc_table_ext_recv", "bsgs_debug_last_kernel", "bsgs_compat_stats_ex", "bsgs_debug_table_owner", "bsgs_prepare", "bsgs_debug_last_batching", "bsgs_debug_last_tiles_per_block", "bsgs_debug_narrow_batching",
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
-    "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym",
+    "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym", "bsgs_kangaroo_setup_sym_keys",
     "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_kangaroo_verify", "bsgs_kangaroo_verify_points", "bsgs_selftest_fe3",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
@@ -179,6 +179,7 @@ def lib():
             "bsgs_debug_xcd_profile": [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
             "bsgs_kangaroo_setup": [vp, u8p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
             "bsgs_kangaroo_setup_sym": [vp, u8p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
+            "bsgs_kangaroo_setup_sym_keys": [vp, u8p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
             "bsgs_kangaroo_upload": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
             "bsgs_kangaroo_upload_list": [vp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(KangarooState)],
             "bsgs_kangaroo_download": [vp, C.c_uint32, C.c_uint32, C.POINTER(KangarooState)],
@@ -280,6 +281,7 @@ class Device:
         self.h = C.c_void_p()
         _chk(lib().bsgs_dev_open(device_id, C.byref(self.h)))
         self.L = lib()
+        self._kang_keyed = False               # the herd is one of kangaroo_setup_sym_keys: states carry a key
 
     def close(self):
         if self.h:
@@ -642,7 +644,7 @@ class Device:
             raise BsgsError("kangaroo_setup: %d jump points and scalars" % KANGAROO_JUMPS)
         xy = b"".join(le32(x) + le32(y) for x, y in jumps)
         _chk(self.L.bsgs_kangaroo_setup(self.h, xy, (C.c_uint64 * KANGAROO_JUMPS)(*scalars), dp, herd, per_thread, record_cap))
-        self._kang_cap = record_cap
+        self._kang_cap, self._kang_keyed = record_cap, False
 
     def kangaroo_setup_sym(self, jumps, scalars, dp, herd, per_thread, record_cap):
         """the symmetric walk (negation map): len(jumps) = R affine points, a power of two in 64..4096; the other kangaroo_* calls then run that walk"""
@@ -650,16 +652,27 @@ class Device:
             raise BsgsError("kangaroo_setup_sym: as many scalars as jump points")
         xy = b"".join(le32(x) + le32(y) for x, y in jumps)
         _chk(self.L.bsgs_kangaroo_setup_sym(self.h, xy, (C.c_uint64 * len(scalars))(*scalars), len(jumps), dp, herd, per_thread, record_cap))
-        self._kang_cap = record_cap
+        self._kang_cap, self._kang_keyed = record_cap, False
+
+    def kangaroo_setup_sym_keys(self, jumps, scalars, dp, herd, per_thread, record_cap):
+        """the symmetric walk for a key list: as kangaroo_setup_sym plus a key per kangaroo.  States of this herd are (x, y, d, flags, key) both ways, and
+        every record's "key" names the key of its kangaroo; kangaroo_set_keys / kangaroo_seed_keys serve it (stored flags: KANGAROO_WILD, no key bits)"""
+        if len(jumps) != len(scalars):
+            raise BsgsError("kangaroo_setup_sym_keys: as many scalars as jump points")
+        xy = b"".join(le32(x) + le32(y) for x, y in jumps)
+        _chk(self.L.bsgs_kangaroo_setup_sym_keys(self.h, xy, (C.c_uint64 * len(scalars))(*scalars), len(jumps), dp, herd, per_thread, record_cap))
+        self._kang_cap, self._kang_keyed = record_cap, True
 
     @staticmethod
     def _kangaroo_states(states):
         arr = (KangarooState * len(states))()
-        for k, (x, y, d, fl) in enumerate(states):
+        for k, (x, y, d, fl, *key) in enumerate(states):
             arr[k].x[:] = le32(x)
             arr[k].y[:] = le32(y)
             arr[k].d[:] = (d % (1 << 128)).to_bytes(16, "little")
             arr[k].flags = fl
+            if key:                                                # (x, y, d, flags, key): a herd of kangaroo_setup_sym_keys; others ignore the word
+                arr[k].reserved[0] = key[0]
         return arr
 
     def kangaroo_upload(self, first, states):
@@ -669,18 +682,23 @@ class Device:
         assert len(idx) == len(states)
         _chk(self.L.bsgs_kangaroo_upload_list(self.h, (C.c_uint32 * len(idx))(*idx), len(idx), self._kangaroo_states(states)))
 
-    def kangaroo_download(self, first, n):
+    def kangaroo_download(self, first, n, reserved=False):
+        """states (x, y, d, flags), of a herd of kangaroo_setup_sym_keys (x, y, d, flags, key); reserved=True: every state followed by the three reserved
+        words of bsgs_kangaroo_state as a tuple, whatever the herd"""
         arr = (KangarooState * n)()
         _chk(self.L.bsgs_kangaroo_download(self.h, first, n, arr))
-        return [(int.from_bytes(bytes(s.x), "little"), int.from_bytes(bytes(s.y), "little"), int.from_bytes(bytes(s.d), "little"), s.flags) for s in arr]
+        keyed = self._kang_keyed
+        return [(int.from_bytes(bytes(s.x), "little"), int.from_bytes(bytes(s.y), "little"), int.from_bytes(bytes(s.d), "little"), s.flags) +
+                ((s.reserved[0],) if keyed else ()) + ((tuple(s.reserved),) if reserved else ()) for s in arr]
 
     def kangaroo_run(self, steps):
-        """one launch of `steps` steps: (records, dropped, kernel ms); a record is {x, d (mod 2^128), kangaroo, flags, step}"""
+        """one launch of `steps` steps: (records, dropped, kernel ms); a record is {x, d (mod 2^128), kangaroo, flags, step, key}, key = the key of
+        the kangaroo in a herd of kangaroo_setup_sym_keys and 0 in every other"""
         cap = self._kang_cap
         recs = (KangarooRecord * cap)()
         n, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_float()
         _chk(self.L.bsgs_kangaroo_run(self.h, steps, recs, cap, C.byref(n), C.byref(dropped), C.byref(ms)))
-        out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step}
+        out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step, "key": r.reserved}
                for r in recs[:n.value]]
         return out, dropped.value, ms.value
 

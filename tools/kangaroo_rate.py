@@ -2,9 +2,10 @@
 """Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
-    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024]] [--out FILE]
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--out FILE]
 
---sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch).
+--sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch); with --keys
+the herd of bsgs_kangaroo_setup_sym_keys, whose kernel entry point reads a kangaroo's key when it writes a record (keys 0..15 dealt out over the herd).
 
 The starts are 65536 distinct points P0 + i*G, repeated over the herd (the walk's cost does not depend on which point a kangaroo stands on; repeats only
 make their DPs coincide)."""
@@ -30,11 +31,11 @@ BYTES_PER_STEP = 32 + 4 + 32 + (32 + 4 + 32 + 32 + 16) + 80
 BYTES_PER_STEP_SYM = BYTES_PER_STEP + 4
 
 
-def vgprs(sym=False):
+def vgprs(sym=False, keys=False):
     try:
         import spill_report
         for r in spill_report.report(tus=["kangaroo"]):
-            if ("kangaroo_sym_kernel<true>" if sym else "kangaroo_kernel<true>") in r["kernel"]:
+            if ("kangaroo_sym_keys_kernel<true>" if keys else "kangaroo_sym_kernel<true>" if sym else "kangaroo_kernel<true>") in r["kernel"]:
                 return r["vgprs"]
     except (SystemExit, Exception):
         return None
@@ -49,8 +50,11 @@ def main():
     ap.add_argument("--per-thread", type=int, default=16)
     ap.add_argument("--sym", action="store_true")
     ap.add_argument("--jumps", type=int, default=1024)
+    ap.add_argument("--keys", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.keys and not a.sym:
+        ap.error("--keys goes with --sym")
     dev = pybsgs.Device(0)
     L = dev.L
     cus = C.c_int()
@@ -60,14 +64,15 @@ def main():
     if a.sym:
         # scalars without additive structure: multiples of one constant satisfy s_a + s_b = s_c + s_d all over and would fill the walk with fruitless cycles
         scal = [splitmix64(j)[1] % (1 << 62) + 1 for j in range(a.jumps)]
-        dev.kangaroo_setup_sym([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
+        (dev.kangaroo_setup_sym_keys if a.keys else dev.kangaroo_setup_sym)([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
     else:
         dev.kangaroo_setup([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
     distinct = 65536
     p = mul(0xC0FFEE << 60)
     one = []
     for i in range(distinct):
-        one.append(p[0].to_bytes(32, "little") + p[1].to_bytes(32, "little") + (i & 0xFFFFFFFF).to_bytes(16, "little") + (i & 1).to_bytes(4, "little") + bytes(12))
+        one.append(p[0].to_bytes(32, "little") + p[1].to_bytes(32, "little") + (i & 0xFFFFFFFF).to_bytes(16, "little") + (i & 1).to_bytes(4, "little") +
+                   ((i >> 1) & 15 if a.keys and i & 1 else 0).to_bytes(4, "little") + bytes(8))
         p = add(p, G)
     blob = b"".join(one) * (n // distinct)
     arr = (pybsgs.KangarooState * n).from_buffer_copy(blob)
@@ -90,10 +95,10 @@ def main():
     wall = time.perf_counter() - t0
     steps = n * a.steps * a.launches
     bps = BYTES_PER_STEP_SYM + 32 * 17 / a.steps if a.sym else BYTES_PER_STEP
-    res = {"what": "kangaroo walk rate, one engine, full herd" + (", symmetric walk, %d jump points" % a.jumps if a.sym else ""), "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp,
+    res = {"what": "kangaroo walk rate, one engine, full herd" + (", symmetric walk, %d jump points" % a.jumps if a.sym else "") + (", a key per kangaroo" if a.keys else ""), "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp,
            "launches": a.launches, "steps_per_s": steps / wall, "steps_per_s_kernel": steps / (sum(kms) / 1e3), "ms_per_launch": sum(kms) / len(kms),
            "ms_per_launch_min": min(kms), "bytes_per_step": bps, "hbm_GBps_implied": steps * bps / (sum(kms) / 1e3) / 1e9,
-           "records_per_launch": nrec / a.launches, "vgprs": vgprs(a.sym)}
+           "records_per_launch": nrec / a.launches, "vgprs": vgprs(a.sym, a.keys)}
     line = json.dumps(res)
     print(line)
     if a.out:
