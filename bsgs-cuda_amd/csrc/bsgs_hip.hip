@@ -130,9 +130,15 @@ extern "C" int bsgs_dev_open(int device_id, bsgs_dev **out)
         d->tiles_per_block = (uint32_t)k;
     }
     HIPCHK(hipGetDeviceProperties(&d->prop, device_id));
+    if (const char *v = getenv("BSGS_LAUNCH_OVERLAP")) d->overlap = atoi(v) != 0;            // A-B and tests: 0 = every launch one kernel on one stream
     HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&d->stream_b, hipStreamNonBlocking));                     // equal priority, all three (bsgs_internal.h)
+    HIPCHK(hipStreamCreateWithFlags(&d->stream_cen, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&d->ev0));
     HIPCHK(hipEventCreate(&d->ev1));
+    HIPCHK(hipEventCreateWithFlags(&d->ev_cen, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&d->ev_a, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&d->ev_b, hipEventDisableTiming));
     if (const char *v = getenv("BSGS_DEBUG_PHASES")) d->debug_flags = (unsigned)atoi(v);     // timing experiments only
     if (const char *v = getenv("BSGS_NARROW_LAUNCHES")) d->narrow_env_off = atoi(v) == 0; // A-B only: 0 = every launch with the default batching
     HIPCHK(hipMalloc(&d->hitbuf, bsgs_hitbuf_bytes(d)));
@@ -141,6 +147,15 @@ extern "C" int bsgs_dev_open(int device_id, bsgs_dev **out)
     HIPCHK(hipStreamSynchronize(d->stream));
     *out = d;
     return BSGS_OK;
+}
+
+hipError_t bsgs_sync_streams(bsgs_dev *d)
+{
+    hipError_t e = hipStreamSynchronize(d->stream), e2 = hipSuccess;
+    if (d->stream_b) e2 = hipStreamSynchronize(d->stream_b);
+    if (e == hipSuccess) e = e2;
+    if (d->stream_cen) e2 = hipStreamSynchronize(d->stream_cen);
+    return e == hipSuccess ? e2 : e;
 }
 
 static void free_table(bsgs_dev *d)
@@ -178,13 +193,15 @@ extern "C" int bsgs_dev_close(bsgs_dev *d)
 {
     if (!d) return BSGS_OK;
     (void)hipSetDevice(d->id);
-    (void)hipStreamSynchronize(d->stream);
+    (void)bsgs_sync_streams(d);
     release_pending(d);
     free_table(d); free_g2(d); bsgs_free_recv(d);
     bsgs_kangaroo_release(d);
     release_grader(d);
     free_reserve(d);
     park_release(d->id);
+    (void)hipEventDestroy(d->ev_cen); (void)hipEventDestroy(d->ev_a); (void)hipEventDestroy(d->ev_b);
+    (void)hipStreamDestroy(d->stream_b); (void)hipStreamDestroy(d->stream_cen);
     if (d->hitbuf) (void)hipFree(d->hitbuf);
     if (d->hit_host) (void)hipHostFree(d->hit_host);
     if (d->cen_dev) (void)hipFree(d->cen_dev);
@@ -347,7 +364,7 @@ static int ensure_chain(bsgs_dev *d, uint64_t tiles, bool full = false)
         const uint64_t piece_bytes = per_tile << lg, npieces = (tiles + (1ull << lg) - 1) >> lg;
         if (npieces <= BSGS_CHAIN_PIECES_MAX) {
             if (!d->chain_pieces.empty() && d->chain_piece_bytes == piece_bytes && d->chain_piece_log == lg && d->chain_pieces.size() >= npieces) return BSGS_OK;
-            HIPCHK(hipStreamSynchronize(d->stream));
+            HIPCHK(bsgs_sync_streams(d));
             free_chain_pieces(d);
             if (d->chain) { (void)hipFree(d->chain); d->chain = nullptr; }
             d->chain_bytes = 0;
@@ -368,14 +385,14 @@ static int ensure_chain(bsgs_dev *d, uint64_t tiles, bool full = false)
         }
     }
     if (!d->chain_pieces.empty()) {                                                 // back to one buffer (a generator kernel, the per-giant kernel)
-        HIPCHK(hipStreamSynchronize(d->stream));
+        HIPCHK(bsgs_sync_streams(d));
         free_chain_pieces(d);
         d->chain_bytes = 0;
     }
     if (d->chain && d->chain_bytes >= bytes) return BSGS_OK;
-    if (d->chain) { HIPCHK(hipStreamSynchronize(d->stream)); (void)hipFree(d->chain); d->chain = nullptr; d->chain_bytes = 0; }
+    if (d->chain) { HIPCHK(bsgs_sync_streams(d)); (void)hipFree(d->chain); d->chain = nullptr; d->chain_bytes = 0; }
     hipError_t e = bsgs_big_malloc(&d->chain, bytes);
-    if (e != hipSuccess && !d->narrow.empty()) { (void)hipGetLastError(); (void)hipStreamSynchronize(d->stream); free_narrow(d); e = bsgs_big_malloc(&d->chain, bytes); }
+    if (e != hipSuccess && !d->narrow.empty()) { (void)hipGetLastError(); (void)bsgs_sync_streams(d); free_narrow(d); e = bsgs_big_malloc(&d->chain, bytes); }
     if (e != hipSuccess) {
         size_t fr = 0, tot = 0;
         (void)hipMemGetInfo(&fr, &tot);
@@ -394,6 +411,9 @@ uint32_t bsgs_auto_tiles_per_launch(const bsgs_dev *d)
     // A launch boundary (ramp: every resident block in the streaming-bound prefix phase; tail) costs ~1.5 ms, i.e. 3.5 % at 48
     // tiles (44.7 ms); the centres live in device memory, so nothing but the chain scratch (8 bytes x giants per tile in flight; 16 with the pair chain)
     // limits a launch: measured 36.0 / 37.3 / 37.5 G giant-steps/s at 48 / 96 / 192 tiles (profiles/r02a_ab_tiles_per_launch.log).
+    // The pair walk's kernel: B = 2 t(96) - t(192) = 3.2 ms per launch, 2.2 % at 192 tiles (profiles/r13a_launch_boundary_parent.txt), 0.2 ms of it the gap between two
+    // kernels on one stream.  launch_tiles now hides most of it by issuing a QUEUED launch of 128 tiles or more as two kernels on two streams; long launches stay the rule
+    // all the same: the halves are kernels of their own, and below 128 tiles nothing is split.
     // Take 4x the fill-the-chip figure when that scratch fits in a third of the free memory, else 2x, else 1x.
     const uint64_t want = (uint64_t)d->prop.multiProcessorCount * 3072;
     uint64_t n = std::min<uint64_t>(std::max<uint64_t>((want + d->Ti - 1) / d->Ti, 1), BSGS_TILES_PER_LAUNCH);
@@ -558,13 +578,11 @@ static const bsgs_dev::Batching *pick_batching(bsgs_dev *d, uint32_t ntiles)
 }
 
 static int quirk_prepare(bsgs_dev *d);
-static int launch_tiles(bsgs_dev *d, const fe *centres_dev, uint32_t ntiles, uint32_t seq)
+// one tile kernel: `ntiles` tiles, the first with sequence number `seq` and centre centres_dev[0..1], on stream `st`, their scratch from tile `tile0` of the launch's scratch on
+static int launch_part(bsgs_dev *d, const bsgs_dev::Batching *nb, hipStream_t st, const fe *centres_dev, uint32_t ntiles, uint32_t seq, uint32_t tile0, bool pair)
 {
     TileArgs A;
-    hipStream_t st = d->stream;
-    const bsgs_dev::Batching *nb = pick_batching(d, ntiles);
     const uint32_t Ti = nb ? nb->Ti : d->Ti, pi = nb ? nb->pi : d->pi;
-    d->last_Ti = Ti; d->last_pi = pi;
     A.g2 = nb ? nb->g2 : d->g2; A.chain = d->chain; A.csr = d->csr; A.lines = d->lines; A.ovf = d->ovf; A.ovf_n = d->ovf_n; A.hitbuf = d->hitbuf;
     A.ht_items = d->ht_items; A.ht_mask = (u32)(d->ht_items - 1); A.pparam = pi; A.T = Ti;
     A.max_hits = d->max_hits; A.tile_seq = seq; A.ntiles = ntiles;
@@ -572,12 +590,16 @@ static int launch_tiles(bsgs_dev *d, const fe *centres_dev, uint32_t ntiles, uin
     A.centres_dev = centres_dev;
     A.digest = d->digest ? d->digest + (uint64_t)seq * Ti * 2 : nullptr;
     A.chain_pad = d->chain_pad; A.chain_mode = 0;
-    for (int k = 0; k < BSGS_CHAIN_PIECES_MAX; k++) A.chain_piece[k] = nullptr;
-    if (!d->chain_pieces.empty()) {                        // chained kernel (ensure_chain)
-        A.chain = nullptr; A.chain_mode = d->chain_piece_log + 1;
-        for (size_t k = 0; k < d->chain_pieces.size(); k++) A.chain_piece[k] = d->chain_pieces[k];
-    }
     const unsigned bs = tile_block(d);
+    const uint32_t group = bsgs_chain_group(d, pi);
+    for (int k = 0; k < BSGS_CHAIN_PIECES_MAX; k++) A.chain_piece[k] = nullptr;
+    if (!d->chain_pieces.empty()) {                        // chained kernel (ensure_chain); part 1 of a split launch starts at the first piece part 0 does not use
+        A.chain = nullptr; A.chain_mode = d->chain_piece_log + 1;
+        for (size_t k = tile0 >> d->chain_piece_log, j = 0; k < d->chain_pieces.size(); k++, j++) A.chain_piece[j] = d->chain_pieces[k];
+    } else if (tile0) {                                    // one buffer: the tiles' scratch areas lie one after the other, as ensure_chain sizes them
+        const uint64_t threads_padded = ((uint64_t)Ti + bs - 1) / bs * bs;
+        A.chain += (uint64_t)tile0 * (threads_padded * pi * 2 / group + d->chain_pad);
+    }
     if ((d->flags & BSGS_FLAG_REFERENCE_QUIRKS) && !d->quirk_host.empty()) {
         // the reference's own P - G arithmetic for the listed giants; bsgs_collect drops the hot loop's records for them
         const uint32_t nfix = (uint32_t)d->quirk_host.size() * ntiles;
@@ -585,13 +607,7 @@ static int launch_tiles(bsgs_dev *d, const fe *centres_dev, uint32_t ntiles, uin
                            (const u32 *)d->quirk_list, (u32)d->quirk_host.size());
         HIPCHK(hipGetLastError());
     }
-    const uint32_t group = bsgs_chain_group(d, pi);
-    // two tiles per block (giant_kernel.hip.h tile_pair_walk): the quad-chain kernels of 64-byte lines, an even number of tiles with the default batching, and both
-    // tiles of a pair in one scratch buffer or piece (pieces of one tile cannot hold a pair).  Narrow launches keep one tile per block: they need the blocks.
-    const bool pair = d->tiles_per_block == 2 && group == 4 && !nb && (ntiles & 1u) == 0 && d->layout == BSGS_TABLE_LINES64 &&
-                      (d->chain_pieces.empty() || d->chain_piece_log >= 1);
     A.tiles_per_block = pair ? 2u : 1u;
-    d->last_tpb = A.tiles_per_block;
     const dim3 grid((unsigned)(((Ti + bs - 1) / bs) * (ntiles / A.tiles_per_block))), block(bs);
     // chained kernel, per wave: two probe slots (QUAD: one probe slot + the two 2 KiB temporaries) + the 2 KiB S stash: 4 blocks fill the 160 KiB of a CU exactly
     const bool l128 = d->layout == BSGS_TABLE_LINES128;
@@ -604,6 +620,40 @@ static int launch_tiles(bsgs_dev *d, const fe *centres_dev, uint32_t ntiles, uin
     else { hipLaunchKernelGGL((giant_tile_kernel<0>), grid, block, 0, st, A); d->last_kernel = "giant_tile_kernel<0>"; }
     HIPCHK(hipGetLastError());
     return BSGS_OK;
+}
+
+// one LOGICAL launch: one kernel, or two kernels on two streams with disjoint halves of the launch's scratch (bsgs_launch_split).  The ramp of a tile kernel (every resident
+// block in the streaming prefix phase) and its ragged tail leave the GPU part idle for ~3 ms per launch; with two in-order queues the blocks of one part take the slots the
+// other part's tail frees, and only one part at a time is in its ramp.  Part i of the next launch follows part i on the same stream, so the scratch needs no event of its own.
+static int launch_tiles(bsgs_dev *d, const fe *centres_dev, uint32_t ntiles, uint32_t seq, bool split_allowed)
+{
+    const bsgs_dev::Batching *nb = pick_batching(d, ntiles);
+    const uint32_t Ti = nb ? nb->Ti : d->Ti, pi = nb ? nb->pi : d->pi;
+    d->last_Ti = Ti; d->last_pi = pi;
+    const uint32_t group = bsgs_chain_group(d, pi);
+    // two tiles per block (giant_kernel.hip.h tile_pair_walk): the quad-chain kernels of 64-byte lines, an even number of tiles with the default batching, and both
+    // tiles of a pair in one scratch buffer or piece (pieces of one tile cannot hold a pair).  Narrow launches keep one tile per block: they need the blocks.
+    const bool pair = d->tiles_per_block == 2 && group == 4 && !nb && (ntiles & 1u) == 0 && d->layout == BSGS_TABLE_LINES64 &&
+                      (d->chain_pieces.empty() || d->chain_piece_log >= 1);
+    d->last_tpb = pair ? 2u : 1u;
+    // what stays one kernel: the synchronous calls (bsgs_run, bsgs_run_walk: split_allowed is false, nothing is queued behind their launch), narrow batchings, the per-giant kernel, the instrumented runs (debug flags, phase probe, digest), launches below two chunks, pieces of one tile
+    uint32_t n0 = 0;
+    if (split_allowed && !nb && group > 1 && !d->debug_flags && !d->phase_probe && !d->digest)
+        n0 = bsgs_launch_split(ntiles, d->chain_pieces.empty() ? 0u : 1u << d->chain_piece_log, (uint32_t)d->chain_pieces.size(), BSGS_TILE_CHUNK, pair);
+    if (n0 != d->split_n0) {
+        // the scratch changes hands between the streams (a ragged last launch, another launch size): each stream that takes over scratch waits for the other's kernels
+        const bool b_waits = n0 != 0, a_waits = d->split_n0 != 0;
+        if (b_waits) HIPCHK(hipEventRecord(d->ev_a, d->stream));
+        if (a_waits) HIPCHK(hipEventRecord(d->ev_b, d->stream_b));
+        if (b_waits) HIPCHK(hipStreamWaitEvent(d->stream_b, d->ev_a, 0));
+        if (a_waits) HIPCHK(hipStreamWaitEvent(d->stream, d->ev_b, 0));
+        d->split_n0 = n0;
+    }
+    d->last_split = n0;
+    if (!n0) return launch_part(d, nb, d->stream, centres_dev, ntiles, seq, 0, pair);
+    int rc = launch_part(d, nb, d->stream, centres_dev, n0, seq, 0, pair);
+    if (rc) return rc;
+    return launch_part(d, nb, d->stream_b, centres_dev + 2 * (uint64_t)n0, ntiles - n0, seq + n0, n0, pair);
 }
 
 static void release_pending(bsgs_dev *d)
@@ -652,8 +702,13 @@ extern "C" int bsgs_quirk_count(bsgs_dev *d, uint32_t *listed)
     return BSGS_OK;
 }
 
-// queue `ntiles` tiles whose centres are already in d->cen_dev[2*queued ...]
-static int enqueue_common(bsgs_dev *d, uint32_t ntiles)
+// the stream the centres of the queued tiles are made on (upload or walk_centres_kernel): its own, so that they never queue behind a tile kernel
+// (the synchronous calls keep everything on the engine's stream: their one kernel would only wait for the other stream's event)
+static hipStream_t centres_stream(bsgs_dev *d, bool split_allowed) { return split_allowed ? d->stream_cen : d->stream; }
+
+// queue `ntiles` tiles whose centres are already in d->cen_dev[2*queued ...] (in the order of centres_stream).  split_allowed: the launches may go out as two kernels
+// on two streams (launch_tiles) and the centres were made on stream_cen; false for the synchronous calls and with BSGS_LAUNCH_OVERLAP=0
+static int enqueue_common(bsgs_dev *d, uint32_t ntiles, bool split_allowed)
 {
     if (d->flags & BSGS_FLAG_REFERENCE_QUIRKS) { int rq = quirk_prepare(d); if (rq) return rq; }
     const uint32_t tpl = bsgs_auto_tiles_per_launch(d);
@@ -663,9 +718,14 @@ static int enqueue_common(bsgs_dev *d, uint32_t ntiles)
         HIPCHK(hipEventRecord(d->ev0, d->stream));
         d->timing_open = true;
     }
+    if (split_allowed) {                                   // both tile streams wait for the centres
+        HIPCHK(hipEventRecord(d->ev_cen, d->stream_cen));
+        HIPCHK(hipStreamWaitEvent(d->stream, d->ev_cen, 0));
+        HIPCHK(hipStreamWaitEvent(d->stream_b, d->ev_cen, 0));
+    }
     for (uint32_t k = 0; k < ntiles; k += tpl) {
         const uint32_t n = std::min<uint32_t>(tpl, ntiles - k);
-        int rc = launch_tiles(d, d->cen_dev + 2 * (uint64_t)(d->queued + k), n, d->queued + k);
+        int rc = launch_tiles(d, d->cen_dev + 2 * (uint64_t)(d->queued + k), n, d->queued + k, split_allowed);
         if (rc) return rc;
         d->launches++;
     }
@@ -688,7 +748,8 @@ extern "C" int bsgs_prepare(bsgs_dev *d)
     return BSGS_OK;
 }
 
-extern "C" int bsgs_enqueue(bsgs_dev *d, const uint8_t *centres, uint32_t ntiles)
+// bsgs_enqueue and bsgs_run: `queued` = more launches may follow before the collect, so a launch may be split (with BSGS_LAUNCH_OVERLAP on)
+static int enqueue_upload(bsgs_dev *d, const uint8_t *centres, uint32_t ntiles, bool queued)
 {
     if (!d || !centres) return fail(BSGS_ERR_ARG, "null");
     if (!d->g2 || !d->layout) return fail(BSGS_ERR_STATE, "upload giants and table first");
@@ -696,11 +757,14 @@ extern "C" int bsgs_enqueue(bsgs_dev *d, const uint8_t *centres, uint32_t ntiles
     HIPCHK(hipSetDevice(d->id));
     int rc = ensure_centres(d, (uint64_t)d->queued + ntiles);
     if (rc) return rc;
+    const bool split_allowed = queued && d->overlap;
     uint8_t *pin = d->cen_pin + (size_t)d->queued * 64;       // a fresh region per enqueue: nothing queued is overwritten
     memcpy(pin, centres, (size_t)ntiles * 64);
-    HIPCHK(hipMemcpyAsync(d->cen_dev + 2 * (uint64_t)d->queued, pin, (size_t)ntiles * 64, hipMemcpyHostToDevice, d->stream));
-    return enqueue_common(d, ntiles);
+    HIPCHK(hipMemcpyAsync(d->cen_dev + 2 * (uint64_t)d->queued, pin, (size_t)ntiles * 64, hipMemcpyHostToDevice, centres_stream(d, split_allowed)));
+    return enqueue_common(d, ntiles, split_allowed);
 }
+
+extern "C" int bsgs_enqueue(bsgs_dev *d, const uint8_t *centres, uint32_t ntiles) { return enqueue_upload(d, centres, ntiles, true); }
 
 // ---- device-side tile walk: replaces GetJob's host point addition + the per-launch upload (1_9_7File.pb:2077-2092, 2435-2445) ----
 extern "C" int bsgs_set_walk(bsgs_dev *d, const uint8_t p0_xy_le[64], const uint8_t stride_xy_le[64])
@@ -724,7 +788,8 @@ extern "C" int bsgs_set_walk(bsgs_dev *d, const uint8_t p0_xy_le[64], const uint
     return BSGS_OK;
 }
 
-extern "C" int bsgs_enqueue_walk(bsgs_dev *d, uint64_t first_tile, uint32_t ntiles)
+// bsgs_enqueue_walk and bsgs_run_walk (`queued` as for enqueue_upload)
+static int enqueue_walked(bsgs_dev *d, uint64_t first_tile, uint32_t ntiles, bool queued)
 {
     if (!d) return fail(BSGS_ERR_ARG, "null");
     if (!d->walk_set) return fail(BSGS_ERR_STATE, "bsgs_set_walk first");
@@ -734,16 +799,19 @@ extern "C" int bsgs_enqueue_walk(bsgs_dev *d, uint64_t first_tile, uint32_t ntil
     HIPCHK(hipSetDevice(d->id));
     int rc = ensure_centres(d, (uint64_t)d->queued + ntiles);
     if (rc) return rc;
-    hipLaunchKernelGGL(walk_centres_kernel, dim3((ntiles + 63) / 64), dim3(64), 0, d->stream, d->walk_p0x, d->walk_p0y,
+    const bool split_allowed = queued && d->overlap;
+    hipLaunchKernelGGL(walk_centres_kernel, dim3((ntiles + 63) / 64), dim3(64), 0, centres_stream(d, split_allowed), d->walk_p0x, d->walk_p0y,
                        (const fe *)d->walk_table, (u64)first_tile, (u32)ntiles, d->cen_dev + 2 * (uint64_t)d->queued, d->hitbuf + BSGS_HIT_WALK_STATUS);
     HIPCHK(hipGetLastError());
-    return enqueue_common(d, ntiles);
+    return enqueue_common(d, ntiles, split_allowed);
 }
+
+extern "C" int bsgs_enqueue_walk(bsgs_dev *d, uint64_t first_tile, uint32_t ntiles) { return enqueue_walked(d, first_tile, ntiles, true); }
 
 extern "C" int bsgs_run_walk(bsgs_dev *d, uint64_t first_tile, uint32_t ntiles, bsgs_hit_ex *hits, uint32_t max_hits,
                              uint32_t *nhits, float *kernel_ms)
 {
-    int rc = bsgs_enqueue_walk(d, first_tile, ntiles);
+    int rc = enqueue_walked(d, first_tile, ntiles, false);
     if (rc) return rc;
     return bsgs_collect(d, hits, max_hits, nhits, kernel_ms);
 }
@@ -776,6 +844,13 @@ extern "C" int bsgs_collect(bsgs_dev *d, bsgs_hit_ex *hits, uint32_t max_hits, u
 {
     if (!d) return fail(BSGS_ERR_ARG, "null");
     HIPCHK(hipSetDevice(d->id));
+    if (d->overlap) {                                      // everything queued, on whichever stream, comes before ev1 and the read-back
+        HIPCHK(hipEventRecord(d->ev_b, d->stream_b));
+        HIPCHK(hipEventRecord(d->ev_cen, d->stream_cen));
+        HIPCHK(hipStreamWaitEvent(d->stream, d->ev_b, 0));
+        HIPCHK(hipStreamWaitEvent(d->stream, d->ev_cen, 0));
+        d->split_n0 = 0;
+    }
     if (d->timing_open) HIPCHK(hipEventRecord(d->ev1, d->stream));
     HIPCHK(hipMemcpyAsync(d->hit_host, d->hitbuf, 64, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -832,7 +907,7 @@ extern "C" int bsgs_collect(bsgs_dev *d, bsgs_hit_ex *hits, uint32_t max_hits, u
 extern "C" int bsgs_run(bsgs_dev *d, const uint8_t *centres, uint32_t ntiles, bsgs_hit_ex *hits, uint32_t max_hits,
                         uint32_t *nhits, float *kernel_ms)
 {
-    int rc = bsgs_enqueue(d, centres, ntiles);
+    int rc = enqueue_upload(d, centres, ntiles, false);
     if (rc) return rc;
     return bsgs_collect(d, hits, max_hits, nhits, kernel_ms);
 }

@@ -38,7 +38,17 @@ struct bsgs_kangaroo {
 
 struct bsgs_dev {
     int id = 0;
-    hipStream_t stream = nullptr;          // the engine's one stream: uploads, relayouts, tile launches, read-backs
+    hipStream_t stream = nullptr;          // the engine's main stream: uploads, relayouts, tile launches (part 0 of a split launch), read-backs
+    // Launch overlap (bsgs_hip.hip enqueue_common): a launch of 2 x BSGS_TILE_CHUNK tiles or more goes out as two kernels with disjoint scratch, part 0 on `stream`, part 1 on
+    // `stream_b`, so that one part's blocks fill the slots the other's ramp and tail leave idle; the centres of the queued tiles are made on `stream_cen`, which never
+    // waits behind a tile kernel.  BSGS_LAUNCH_OVERLAP=0: one kernel per launch, everything on `stream`.
+    hipStream_t stream_b = nullptr, stream_cen = nullptr;
+    hipEvent_t ev_cen = nullptr, ev_a = nullptr, ev_b = nullptr;      // ordering only (no timing): centres ready; `stream` / `stream_b` reached this point
+    bool overlap = true;                   // BSGS_LAUNCH_OVERLAP
+                                           // (the synchronous calls bsgs_run / bsgs_run_walk never split: their launch is collected at once, and two kernels that start together
+                                           // on an idle GPU ramp and end together: 146.4 against 145.4 ms, profiles/r13a_lone_launches.log)
+    uint32_t split_n0 = 0;                 // first tile of part 1 in the most recent launch; 0 = that launch was one kernel on `stream` (nothing newer runs on `stream_b`)
+    uint32_t last_split = 0;               // the same, kept across bsgs_collect (test library: bsgs_debug_last_split)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     unsigned debug_flags = 0;
     bool phase_probe = false;
@@ -149,6 +159,26 @@ void bsgs_free_recv(bsgs_dev *d);                            // receive buffers 
 int bsgs_set_geometry(bsgs_dev *d, uint32_t t, uint32_t b, uint32_t p);      // (re)allocates the giants for this geometry and picks the engine's own batching
 uint32_t bsgs_chain_group(const bsgs_dev *d, uint32_t pi);   // giants per stored running product of the tile kernel a launch with batch length pi takes (4 / 2 chained, 1 per-giant)
 uint32_t bsgs_auto_tiles_per_launch(const bsgs_dev *d);      // the launch size in effect
+hipError_t bsgs_sync_streams(bsgs_dev *d);                   // drains the tile streams and the centres stream: before the scratch, the centres or the hit buffer change hands
+// The split of a launch of n tiles into two kernels: part 0 = tiles [0, n0), part 1 = [n0, n); 0 = the launch stays one kernel.  piece_tiles = tiles per scratch piece
+// (0: the scratch is one buffer), pieces = how many there are, chunk = BSGS_TILE_CHUNK, pair = the launch walks two tiles per block (both parts must be even then).
+// Pieces: the piece boundary nearest n / 2, so that part 1's pieces are none of part 0's.  One buffer: n / 2, made even when n is even.
+static inline uint32_t bsgs_launch_split(uint32_t n, uint32_t piece_tiles, uint32_t pieces, uint32_t chunk, bool pair)
+{
+    if (chunk == 0 || n < 2 * (uint64_t)chunk) return 0;
+    uint32_t n0;
+    if (piece_tiles) {
+        if (piece_tiles < 2) return 0;                                             // pieces of one tile
+        n0 = (uint32_t)(((uint64_t)(n / 2) + piece_tiles / 2) / piece_tiles * piece_tiles);
+        if (n0 / piece_tiles >= pieces || ((uint64_t)n + piece_tiles - 1) / piece_tiles > pieces) return 0;
+    } else {
+        n0 = n / 2;
+        if ((n & 1u) == 0 && (n0 & 1u)) n0++;
+    }
+    if (n0 == 0 || n0 >= n) return 0;
+    if (pair && ((n0 | (n - n0)) & 1u)) return 0;
+    return n0;
+}
 static inline bool bsgs_lines_layout(const bsgs_dev *d) { return d->layout == BSGS_TABLE_LINES64 || d->layout == BSGS_TABLE_LINES128; }
 static inline size_t bsgs_hitbuf_bytes(const bsgs_dev *d) { return 64 + (size_t)d->max_hits * 16; }
 static inline void bsgs_le_to_fe(fe &f, const uint8_t *le) { memcpy(f.v, le, 32); }

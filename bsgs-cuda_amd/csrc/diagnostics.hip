@@ -53,10 +53,8 @@ extern "C" int bsgs_tune_placement(bsgs_dev *d, uint32_t candidates, float *ms_o
     HIPCHK(hipSetDevice(d->id));
     const uint32_t tpl = bsgs_auto_tiles_per_launch(d);
     auto launch = [&](float *ms) -> int {
-        int rc = bsgs_enqueue_walk(d, 0, tpl);
-        if (rc) return rc;
         uint32_t n = 0;
-        rc = bsgs_collect(d, nullptr, 0, &n, ms);
+        int rc = bsgs_run_walk(d, 0, tpl, nullptr, 0, &n, ms);
         return rc == BSGS_ERR_OVERFLOW ? BSGS_OK : rc;
     };
     auto timed = [&](float *ms) -> int {                   // one warm launch, then two timed ones

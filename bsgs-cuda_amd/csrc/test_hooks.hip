@@ -1,5 +1,5 @@
 // test_hooks.hip -- TEST BUILD ONLY: linked into build/libbsgs_hip_test.so, never into the shipped libbsgs_hip.so (Makefile).  The corrupted replica that the
-// verification must catch, and buffer re-allocation for the placement experiments (tools/placement_probe.py).
+// verification must catch, buffer re-allocation for the placement experiments (tools/placement_probe.py), and the rule that splits a launch into two kernels.
 #define BSGS_TEST_HOOKS 1
 #include "bsgs_internal.h"
 #include "support_kernels.hip.h"
@@ -71,5 +71,22 @@ extern "C" int bsgs_debug_realloc(bsgs_dev *d, int which, uint64_t spacer_bytes)
     }
     if (spacer) (void)hipFree(spacer);
     if (e != hipSuccess) return fail(BSGS_ERR_HIP, "debug_realloc: %s", hipGetErrorString(e));
+    return BSGS_OK;
+}
+
+// the rule launch_tiles splits a launch by (bsgs_internal.h bsgs_launch_split), no device needed: *first_of_part1 = n0, 0 = the launch stays one kernel
+// (tests/test_launch_split_model.py)
+extern "C" int bsgs_debug_launch_split(uint32_t ntiles, uint32_t tiles_per_piece, uint32_t pieces, uint32_t chunk, uint32_t pair_walk, uint32_t *first_of_part1)
+{
+    if (!first_of_part1) return fail(BSGS_ERR_ARG, "null");
+    *first_of_part1 = bsgs_launch_split(ntiles, tiles_per_piece, pieces, chunk, pair_walk != 0);
+    return BSGS_OK;
+}
+
+// first tile of part 1 of the most recent launch, 0 = it was one kernel
+extern "C" int bsgs_debug_last_split(bsgs_dev *d, uint32_t *first_of_part1)
+{
+    if (!d || !first_of_part1) return fail(BSGS_ERR_ARG, "null");
+    *first_of_part1 = d->last_split;
     return BSGS_OK;
 }

@@ -31,7 +31,7 @@ NATIVE_SYMBOLS = [
     "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_kangaroo_verify", "bsgs_kangaroo_verify_points", "bsgs_selftest_fe3",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
-TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc"]
+TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
 TEST_LIB_PATH = os.path.join(PKG_ROOT, "build", "libbsgs_hip_test.so")
 COMPAT_SYMBOLS = [
     "cuInit", "cuDeviceGetCount", "cuDeviceGet", "cuDeviceGetName", "cuDeviceTotalMem_v2", "cuDeviceComputeCapability",
@@ -409,6 +409,14 @@ class Device:
     def debug_corrupt_table(self, byte_offset, xor_mask=1):
         """TEST BUILD hook: flip bits of one byte of the installed table (what the verification must catch)"""
         _chk(self._test_hook("bsgs_debug_corrupt_table")(self.h, byte_offset, xor_mask))
+
+    def debug_last_split(self):
+        """TEST BUILD hook: first tile of part 1 of the most recent launch (two kernels on two streams, bsgs_hip.hip launch_tiles), 0 = it was one kernel"""
+        n0 = C.c_uint32()
+        fn = self._test_hook("bsgs_debug_last_split")
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        _chk(fn(self.h, C.byref(n0)))
+        return n0.value
 
     def sample_g2(self, indices):
         """giants by number as (x, y) integer pairs (what a host compares with (i + 1) * ADDPUBG before it searches: checkGiantArr 1_9_7File.pb:1524-1559)"""
