@@ -15,7 +15,7 @@ int bsgs_fail(int code, const char *fmt, ...);
 #define fail bsgs_fail
 
 // kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip, kangaroo_seed_keys.hip: the comb table, the staging of a seed call and the key list;
-// kangaroo_verify.hip: the one Q of a call and the list of failures
+// kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
     u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
@@ -34,6 +34,9 @@ struct bsgs_kangaroo {
     u32x4 *verify_q = nullptr;             // bsgs_kangaroo_verify*: the call's one Q, x || y (64 bytes)
     u32 *verify_out = nullptr;             // {positions that failed, then the first verify_cap of them}
     uint32_t verify_cap = 0;
+    u32x4 *tames = nullptr;                // bsgs_kangaroo_tames_install: the image, tames_lines lines of 64 bytes (a power of two), tames_n entries
+    u32 *tames_rec = nullptr;              // the records of a launch that matched, laid out as rec
+    uint64_t tames_lines = 0, tames_n = 0;
 };
 
 struct bsgs_dev {
@@ -185,6 +188,9 @@ static inline void bsgs_le_to_fe(fe &f, const uint8_t *le) { memcpy(f.v, le, 32)
 uint64_t bsgs_ovf_slots(uint64_t entries);                   // size of the overflow hash set for `entries` keys (power of two, load <= 1/2)
 int bsgs_ovf_fill(bsgs_dev *d, const u64 *list, uint64_t n, u64 *table, uint64_t slots);   // table := hash set of list[0..n)
 int bsgs_kangaroo_split_keys(bsgs_dev *d, const u32 *idx_dev, uint32_t first, uint32_t n);      // kangaroo.hip: flags WILD | key << 8 of the kangaroos just seeded -> flags, key[]
+int bsgs_kangaroo_launch(bsgs_dev *d, uint32_t steps);     // kangaroo.hip: the three steps of bsgs_kangaroo_run, shared with bsgs_kangaroo_run_tames (kangaroo_tames.hip)
+int bsgs_kangaroo_finish(bsgs_dev *d, uint64_t *count, const u32 *other, uint64_t *other_count, float *kernel_ms);
+int bsgs_kangaroo_copy_out(bsgs_dev *d, const u32 *buf, uint64_t held, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *given);
 void bsgs_kangaroo_release(bsgs_dev *d);                     // kangaroo.hip: frees the herd (bsgs_dev_close, a new bsgs_kangaroo_setup)
 // hand a finished "lines + overflow list" table to the engine (it becomes the owner of both buffers)
 int bsgs_install_lines(bsgs_dev *d, u32x4 *lines, int lplog, u64 *ovf, uint64_t ovf_n, uint64_t ht_items, uint64_t w,

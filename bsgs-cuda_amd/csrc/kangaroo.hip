@@ -368,7 +368,8 @@ void bsgs_kangaroo_release(bsgs_dev *d)
     bsgs_kangaroo *k = d->kangaroo;
     if (!k) return;
     for (void *p : {(void *)k->st, (void *)k->chain, (void *)k->table, (void *)k->staging, (void *)k->flags, (void *)k->rec, (void *)k->idx, (void *)k->comb,
-                    (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out, (void *)k->mark, (void *)k->keys, (void *)k->verify_q, (void *)k->verify_out})
+                    (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out, (void *)k->mark, (void *)k->keys, (void *)k->verify_q, (void *)k->verify_out, (void *)k->tames,
+                    (void *)k->tames_rec})
         if (p) (void)hipFree(p);
     if (k->rec_host) (void)hipHostFree(k->rec_host);
     delete k;
@@ -493,12 +494,10 @@ extern "C" int bsgs_kangaroo_download(bsgs_dev *d, uint32_t first, uint32_t n, b
     return BSGS_OK;
 }
 
-extern "C" int bsgs_kangaroo_run(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *dropped, float *kernel_ms)
+// one launch of the walk on the engine's stream, timed from ev0; bsgs_kangaroo_run and bsgs_kangaroo_run_tames (kangaroo_tames.hip) share the three steps
+int bsgs_kangaroo_launch(bsgs_dev *d, uint32_t steps)
 {
-    if (!d || !nrecs) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = d->kangaroo;
-    if (!k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
-    HIPCHK(hipSetDevice(d->id));
     KangArgs A;
     A.st = k->st; A.flags = k->flags; A.chain = k->chain; A.table = k->table; A.rec = k->rec;
     A.N = k->N; A.T = k->T; A.G = k->G; A.steps = steps; A.cap = k->cap;
@@ -518,20 +517,45 @@ extern "C" int bsgs_kangaroo_run(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_reco
     } else if (k->block == 256u) hipLaunchKernelGGL(kangaroo_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_LDS, d->stream, A);
     else hipLaunchKernelGGL(kangaroo_kernel<false>, dim3(k->T / 64u), dim3(64), KANG_LDS, d->stream, A);
     HIPCHK(hipGetLastError());
+    return BSGS_OK;
+}
+// ev1 behind what has been launched since bsgs_kangaroo_launch, then the count of records the walk produced (and the count at the head of `other`, a
+// second record buffer, when there is one) and the synchronisation
+int bsgs_kangaroo_finish(bsgs_dev *d, uint64_t *count, const u32 *other, uint64_t *other_count, float *kernel_ms)
+{
+    bsgs_kangaroo *k = d->kangaroo;
     HIPCHK(hipEventRecord(d->ev1, d->stream));
-    uint64_t count = 0;
-    HIPCHK(hipMemcpyAsync(&count, k->rec, 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(count, k->rec, 8, hipMemcpyDeviceToHost, d->stream));
+    if (other) HIPCHK(hipMemcpyAsync(other_count, other, 8, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
-    const uint64_t held = std::min<uint64_t>(count, k->cap);
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    return BSGS_OK;
+}
+// the first min(held, max_recs) records of a record buffer -> recs (nullptr: none)
+int bsgs_kangaroo_copy_out(bsgs_dev *d, const u32 *buf, uint64_t held, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *given)
+{
+    bsgs_kangaroo *k = d->kangaroo;
     const uint64_t give = recs ? std::min<uint64_t>(held, max_recs) : 0;
     if (give) {
-        HIPCHK(hipMemcpyAsync(k->rec_host, (char *)k->rec + KANG_REC_HEADER, give * 64, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(k->rec_host, (const char *)buf + KANG_REC_HEADER, give * 64, hipMemcpyDeviceToHost, d->stream));
         HIPCHK(hipStreamSynchronize(d->stream));
         memcpy(recs, k->rec_host, give * 64);
     }
-    *nrecs = (uint32_t)give;
-    if (dropped) *dropped = count - give;
-    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    *given = (uint32_t)give;
+    return BSGS_OK;
+}
+
+extern "C" int bsgs_kangaroo_run(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *dropped, float *kernel_ms)
+{
+    if (!d || !nrecs) return fail(BSGS_ERR_ARG, "null");
+    bsgs_kangaroo *k = d->kangaroo;
+    if (!k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
+    HIPCHK(hipSetDevice(d->id));
+    if (int rc = bsgs_kangaroo_launch(d, steps)) return rc;
+    uint64_t count = 0;
+    if (int rc = bsgs_kangaroo_finish(d, &count, nullptr, nullptr, kernel_ms)) return rc;
+    if (int rc = bsgs_kangaroo_copy_out(d, k->rec, std::min<uint64_t>(count, k->cap), recs, max_recs, nrecs)) return rc;
+    if (dropped) *dropped = count - *nrecs;
     return BSGS_OK;
 }
 

@@ -81,7 +81,11 @@ void usage(const Config &c)
            "-kcpuseed    Kangaroo: compute the kangaroos' start points on the host CPU instead of the GPU (same herd; for cross-checks)\n"
            "-ksym        Kangaroo: the symmetric walk (negation map: P and -P are one point of the walk; wild-wild collisions solve too; cycles are retired and re-seeded)\n"
            "-kjumps R    Kangaroo -ksym: jump points, a power of two 64..4096 (default 1024)\n"
-           "-kjumpscale F  Kangaroo -ksym: mean jump = F * N_k sqrt(W) / 4 (default 2)\n");
+           "-kjumpscale F  Kangaroo -ksym: mean jump = F * N_k sqrt(W) / 4 (default 2)\n"
+           "-ktamesgen F Kangaroo: make a tame table of -ktn T distinguished points of the range [-pk, -pke] and write it to F (nothing else is saved; no -wl, -wt)\n"
+           "-ktn T       Kangaroo -ktamesgen: entries of the table, 1..2^31\n"
+           "-ktames F    Kangaroo: search -pb or every key of -infile with the tame table F of this range: all kangaroos wild, records matched against the table on the GPU\n"
+           "             (the table is verified on the GPU at load, -noverify skips; not with -ksym, -kwalk sym, -wl, -dp; nothing is saved)\n");
 }
 
 Config parse_args(int argc, char **argv)

@@ -247,7 +247,7 @@ const double KSYM_JUMPSCALE = 2.0;                 // DESIGN.md 10, "jump scale"
 KangConfig kang::parse_kangaroo_args(int argc, char **argv)
 {
     KangConfig c;
-    bool ksym = false, kwalk_sym = false;
+    bool ksym = false, kwalk_sym = false, wt_given = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         for (auto &ch : a) ch = (char)tolower(ch);
@@ -264,7 +264,10 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-kn") c.kn = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-kseed") { c.seed = strtoull(next().c_str(), nullptr, 0); c.seed_given = true; }
         else if (a == "-wl") c.wl = next();
-        else if (a == "-wt") c.wt = std::max(30, atoi(next().c_str()));
+        else if (a == "-wt") { c.wt = std::max(30, atoi(next().c_str())); wt_given = true; }
+        else if (a == "-ktamesgen") c.ktamesgen = next();
+        else if (a == "-ktames") c.ktames = next();
+        else if (a == "-ktn") { c.ktn = strtoull(next().c_str(), nullptr, 0); if (!c.ktn || c.ktn > (1ull << 31)) die("-ktn must be 1..2^31"); }
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
         else if (a == "-ksym") ksym = true;
@@ -275,6 +278,26 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-w" || a == "-htsz" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table)");
         else die("Unknown parameter with -kangaroo: " + a);
     }
+    // a tame table (host_kangaroo_tames.cpp): made and used by the plain walk, never saved; every refusal before any device is looked for
+    if (!c.ktamesgen.empty() || !c.ktames.empty()) {
+        const std::string flag = c.ktames.empty() ? "-ktamesgen" : "-ktames";
+        if (!c.ktamesgen.empty() && !c.ktames.empty()) die("-ktamesgen and -ktames exclude each other (make the table first, then search with it)");
+        if (ksym) die("-kangaroo " + flag + " cannot be combined with -ksym (a tame table belongs to the plain walk)");
+        if (kwalk_sym) die("-kangaroo " + flag + " cannot be combined with -kwalk sym (a tame table belongs to the plain walk)");
+        if (!c.wl.empty()) die("-kangaroo " + flag + " cannot be combined with -wl (nothing is saved, so nothing is resumed)");
+        if (c.ktames.empty()) {
+            if (wt_given) die("-kangaroo -ktamesgen cannot be combined with -wt (nothing is saved but the table)");
+            if (!c.ktn) die("-kangaroo -ktamesgen needs -ktn (the entries of the table)");
+            if (c.pub_given || !c.infile.empty()) die("-kangaroo -ktamesgen takes no -pb or -infile (a tame table serves every key of its range)");
+        } else {
+            if (c.dp >= 0) die("-kangaroo -ktames cannot be combined with -dp (the table names its own)");
+            if (c.ktn) die("-ktn belongs to -ktamesgen");
+            if (c.pub_given && !c.infile.empty()) die("-kangaroo: -pb and -infile exclude each other (the keys come from the file)");
+            if (!c.pub_given && c.infile.empty()) die("-kangaroo -ktames needs -pb or -infile");
+        }
+        return c;
+    }
+    if (c.ktn) die("-ktn belongs to -ktamesgen");
     // -kwalk sym: the symmetric walk of whatever is searched -- one key (-pb; the same as -ksym) or the list of -infile
     c.symlist = kwalk_sym && !c.infile.empty();
     c.sym = ksym || (kwalk_sym && c.infile.empty());
@@ -464,6 +487,7 @@ int kangaroo_main(int argc, char **argv)
 {
     printf("BSGS MI355X kangaroo mode on %s\n", bsgs_version());
     const KangConfig c = parse_kangaroo_args(argc, argv);
+    if (!c.ktamesgen.empty() || !c.ktames.empty()) return kangaroo_tames_main(c);
     if (!c.infile.empty()) return c.symlist ? kangaroo_symlist_main(c) : kangaroo_multi_main(c);
     Affine P;
     if (!hs::parse_pubkey(P, c.pub) || !hs::on_curve(P)) die("Invalid Public Key (-pb) length!!!");

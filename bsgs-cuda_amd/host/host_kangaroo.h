@@ -72,6 +72,8 @@ struct KangConfig {
     uint32_t jumps = 0;                            // -kjumps: jump points of the symmetric walk (default 1024; resumed: from the work file)
     double jumpscale = 0.0;                        // -kjumpscale: mean jump = scale * N_k sqrt(W) / 4 (default KSYM_JUMPSCALE; resumed: from the work file)
     bool verify = true;                            // -noverify: herds and the saved table are not checked against their offsets (at -wl, before every save)
+    std::string ktamesgen, ktames;                 // -ktamesgen FILE: make a tame table; -ktames FILE: search with one (host_kangaroo_tames.cpp)
+    uint64_t ktn = 0;                              // -ktn: entries of the table -ktamesgen makes
 };
 KangConfig parse_kangaroo_args(int argc, char **argv);
 
@@ -123,3 +125,4 @@ std::vector<std::string> split_commas(const std::string &rec);
 
 int kangaroo_multi_main(const kang::KangConfig &c);      // host_kangaroo_multi.cpp: -kangaroo -infile
 int kangaroo_symlist_main(const kang::KangConfig &c);    // host_kangaroo_symlist.cpp: -kangaroo -infile -kwalk sym
+int kangaroo_tames_main(const kang::KangConfig &c);      // host_kangaroo_tames.cpp: -kangaroo -ktamesgen, -kangaroo -ktames

@@ -84,11 +84,11 @@ void Prologue::complete(const KangConfig &c, Mode &mode)
     int cus = 256;
     { bsgs_dev *d = nullptr; CK(bsgs_dev_open(gpus[0], &d)); bsgs_dev_cu_count(d, &cus); bsgs_dev_close(d); }
     // defaults from W (plan_herd); then the expected total, the launch length and the record buffer, which depend on it
-    pl = plan_herd(sqrtW, (uint32_t)gpus.size(), cus, resume ? (int)wf.h.dp : c.dp, c.kn);
+    pl = plan_herd(sqrtW, (uint32_t)gpus.size(), cus, resume ? (int)wf.h.dp : mode.dp_fixed >= 0 ? mode.dp_fixed : c.dp, c.kn);
     if (resume) { pl.kn = wf.h.herd; pl.G = wf.h.per_thread; }        // the plan of the run that saved, not this GPU's
     if (pl.kn > (1ull << 26)) die("-kn: at most 2^26 kangaroos per engine");
     const double Nk = (double)pl.kn * pl.engines;
-    pl.expected = 2.0 * sqrtW + Nk * std::ldexp(1.0, (int)pl.dp);
+    pl.expected = (mode.expected > 0.0 ? mode.expected : 2.0 * sqrtW) + Nk * std::ldexp(1.0, (int)pl.dp);
     pl.S = (uint32_t)std::max(mode.min_launch, std::min(1024.0, pl.expected / Nk / 8.0));
     pl.cap = (uint32_t)std::min<double>(1u << 22, 2.0 * (double)pl.kn * pl.S / std::ldexp(1.0, (int)pl.dp) + 65536.0);
     uint64_t seed = c.seed;
@@ -100,12 +100,12 @@ void Prologue::complete(const KangConfig &c, Mode &mode)
     wh.fingerprint = mode.fingerprint(*this, wh);
 
     rng = seed;
-    const double mean = std::max(1.0, std::min(std::ldexp(1.0, 62), mode.jumpscale * Nk * sqrtW / 4.0));
+    const double mean = mode.mean_jump > 0.0 ? mode.mean_jump : std::max(1.0, std::min(std::ldexp(1.0, 62), mode.jumpscale * Nk * sqrtW / 4.0));
     js.resize(mode.jumps);
     jxy.resize(64 * (size_t)mode.jumps);
     for (uint32_t j = 0; j < mode.jumps; j++) {
         const uint64_t span = (uint64_t)(2.0 * mean) > 1 ? (uint64_t)(2.0 * mean) - 1 : 1;
-        js[j] = 1 + splitmix64(rng) % span;
+        js[j] = mode.jump_scalars ? mode.jump_scalars[j] : 1 + splitmix64(rng) % span;
         hs::affine_to_le(hs::point_mul(hs::G, hs::fe_from_u64(js[j])), &jxy[64 * (size_t)j], &jxy[64 * (size_t)j + 32]);
     }
     herds.resize(pl.engines);
@@ -248,7 +248,7 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
         if (!sh.stop.load()) {
             uint32_t n = 0;
             uint64_t dropped = 0;
-            if (bsgs_kangaroo_run(dev, p.pl.S, recs.data(), p.pl.cap, &n, &dropped, nullptr) != BSGS_OK) { bad("bsgs_kangaroo_run"); break; }
+            if (mode.launch(dev, e, p.pl.S, recs.data(), p.pl.cap, &n, &dropped, sh) != BSGS_OK) { bad("bsgs_kangaroo_run"); break; }
             const uint64_t total = (sh.steps += kn * p.pl.S);
             sh.dropped += dropped;
             { std::lock_guard<std::mutex> lk(sh.q_m); sh.queue.emplace_back(e, std::vector<bsgs_kangaroo_record>(recs.begin(), recs.begin() + n)); }
@@ -260,7 +260,7 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
         // the herd as it stands leaves the device between two launches when a save is requested, and at the end when the search is not done (the last save)
         const bool stopped = sh.stop.load();
         bool want = sh.save_req.load();
-        if (stopped) { std::lock_guard<std::mutex> lt(sh.tab_m); want = !mode.done(); }
+        if (stopped) { std::lock_guard<std::mutex> lt(sh.tab_m); want = mode.saves && !mode.done(); }
         if (want && check && !sh.failed.load()) {                      // before every save: a herd that went wrong never replaces a good file
             const auto ts = Clock::now();
             uint32_t at = 0;
@@ -353,7 +353,7 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
             }
             if (mode.give_up(sh.steps.load())) { gave_up = true; sh.stop = true; }
         }
-        if (!sh.stop.load() && std::chrono::duration<double>(now - last_save).count() >= (double)c.wt) {
+        if (mode.saves && !sh.stop.load() && std::chrono::duration<double>(now - last_save).count() >= (double)c.wt) {
             // -wt: every engine parks between two launches with its herd downloaded and its last records queued; the collector empties the queue; then
             // table, counters, stream, herds and re-seed lists belong to one moment of the search
             const auto ts = Clock::now();
@@ -383,9 +383,9 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
     signal(SIGINT, SIG_DFL);
     signal(SIGTERM, SIG_DFL);
     if (!sh.err.empty()) die(sh.err);
-    if (mode.done()) { remove(p.work_path.c_str()); return DONE; }     // a stale file never outlives its job
+    if (mode.done()) { if (mode.saves) remove(p.work_path.c_str()); return DONE; }     // a stale file never outlives its job
     bool have = true;
     for (uint32_t e = 0; e < pl.engines; e++) have = have && sh.saved[e].size() == pl.kn;
-    if (have) write_state();                                           // engines joined, queue drained: the state is final
+    if (have && mode.saves) write_state();                                           // engines joined, queue drained: the state is final
     return gave_up ? GAVE_UP : interrupted ? INTERRUPTED : c.ksteps && sh.steps.load() >= c.ksteps ? BUDGET : ENDED;
 }

@@ -65,6 +65,13 @@ public:
     uint32_t version = WORK_VERSION, jumps = BSGS_KANGAROO_JUMPS;
     double min_launch = 8.0, jumpscale = 1.0;
     const char *wl_flag = "-kangaroo -wl", *wl_kind = "a kangaroo.work file";
+    // what a mode that walks with a table made earlier sets before Prologue::complete (host_kangaroo_tames.cpp): the dp of that table (-1: the command line's
+    // or the plan's), the mean jump (0: jumpscale * N_k sqrt(W) / 4), the jump scalars themselves (null: drawn from the seed), the steps the run expects before
+    // the DP overhead (0: 2 sqrt(W)), and whether the run writes kangaroo.work at all
+    int dp_fixed = -1;
+    double mean_jump = 0.0, expected = 0.0;
+    const uint64_t *jump_scalars = nullptr;
+    bool saves = true;
     const char *herd_label = "herds (GPU), engine ";                  // the [startup] line of a herd seeded in its engine's thread
     virtual std::string fingerprint(const Prologue &p, const WorkHeader &h) const = 0;
     // between the work file and the devices: the mode's own resume checks ("Recovery file was made with other settings"), its header fields, its first
@@ -77,6 +84,13 @@ public:
     // under sh.tab_m.  One record of engine e into the table: kangaroos to start afresh go on sh's lists, a finished search sets sh.stop; false: the rest of
     // the batch is not looked at
     virtual bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &sh) = 0;
+    // in an engine's thread: one launch of `steps` steps of engine e's herd, its records to recs.  Today's call; a mode whose records are matched on the
+    // device names the call that does that
+    virtual int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &sh)
+    {
+        (void)e; (void)sh;
+        return bsgs_kangaroo_run(dev, steps, recs, cap, n, dropped, nullptr);
+    }
     // what the verification needs (bsgs_kangaroo_verify, bsgs_kangaroo_verify_points; set in before_devices): the one Q of every wild kangaroo, or null: the
     // key list the engines got in setup(); why the device cannot check this search, or null; the flags a table entry's type or owner word stands for
     const uint8_t *verify_q = nullptr;

@@ -1,0 +1,556 @@
+// host_kangaroo_tames.cpp -- the tame half of the kangaroo search done once and kept (include/bsgs_hip.h "Kangaroo, tame table" states the rule;
+// tests/kangaroo_tames_model.py restates it): the table file, the plan, and the two modes behind the driver's seam (host_kangaroo_run.h):
+//   bsgs_mi355x -kangaroo -ktamesgen FILE -ktn T   an all-tame herd walks until the host's map holds T distinguished points, which are written sorted
+//   bsgs_mi355x -kangaroo -ktames FILE             an all-wild herd, shared over the keys, walks with the file's jumps; each launch's records are matched
+//                                                 against the table on the device (bsgs_kangaroo_run_tames) and only the matches come back
+// Neither writes kangaroo.work.  TamesRule is the search rule without a device: -selftest kangaroo-tames-search drives it with scripted records.
+#include "host_kangaroo_list.h"
+
+#include <iostream>
+
+namespace {
+using namespace kang;
+
+const char TAMES_MAGIC[9] = "KANGTAME";
+const uint32_t TAMES_VERSION = 1;
+const size_t TAMES_HEADER = 624, TAMES_ENTRY = 24;
+
+struct TamesFile {
+    uint32_t dp = 0;
+    Scalar lo, hi;
+    uint64_t steps = 0, seed = 0, m = 0;
+    std::vector<uint64_t> js, x;                   // the 64 jump scalars; the entries' low 64 bits of x, strictly ascending
+    std::vector<i128> d;                           // and their offsets
+};
+
+bool write_tames(const std::string &path, const TamesFile &f)
+{
+    std::vector<uint8_t> b(TAMES_HEADER + TAMES_ENTRY * f.x.size(), 0);
+    const uint64_t T = f.x.size();
+    memcpy(&b[0], TAMES_MAGIC, 8); memcpy(&b[8], &TAMES_VERSION, 4); memcpy(&b[12], &f.dp, 4);
+    hs::fe_to_le(f.lo, &b[16]); hs::fe_to_le(f.hi, &b[48]);
+    memcpy(&b[80], &T, 8); memcpy(&b[88], &f.steps, 8); memcpy(&b[96], &f.seed, 8); memcpy(&b[104], &f.m, 8);
+    memcpy(&b[112], f.js.data(), 512);
+    for (uint64_t i = 0; i < T; i++) { memcpy(&b[TAMES_HEADER + TAMES_ENTRY * i], &f.x[i], 8); memcpy(&b[TAMES_HEADER + TAMES_ENTRY * i + 8], &f.d[i], 16); }
+    const std::string tmp = path + ".temp";
+    { std::ofstream o(tmp, std::ios::binary); o.write((const char *)b.data(), (std::streamsize)b.size()); if (!o) return false; }
+    return rename(tmp.c_str(), path.c_str()) == 0;
+}
+
+// "" when the file is a complete tame table, else what is wrong with it; the file is only read
+std::string read_tames(const std::string &path, TamesFile &f)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in) return "cannot open " + path;
+    std::vector<uint8_t> b((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    if (b.size() < 8 || memcmp(b.data(), TAMES_MAGIC, 8) != 0) return path + " is not a tame table (magic)";
+    uint32_t version = 0;
+    if (b.size() >= 12) memcpy(&version, &b[8], 4);
+    if (b.size() < 12 || version != TAMES_VERSION) return path + ": tame table version " + std::to_string(version) + ", this program reads version " + std::to_string(TAMES_VERSION);
+    uint64_t T = 0;
+    if (b.size() >= TAMES_HEADER) memcpy(&T, &b[80], 8);
+    if (b.size() < TAMES_HEADER || !T || T > (1ull << 31) || b.size() != TAMES_HEADER + TAMES_ENTRY * T) return path + ": wrong length for a tame table (" + std::to_string(b.size()) + " bytes)";
+    memcpy(&f.dp, &b[12], 4);
+    if (f.dp > 32) return path + ": -dp " + std::to_string(f.dp);
+    f.lo = hs::fe_from_le(&b[16]); f.hi = hs::fe_from_le(&b[48]);
+    memcpy(&f.steps, &b[88], 8); memcpy(&f.seed, &b[96], 8); memcpy(&f.m, &b[104], 8);
+    f.js.resize(BSGS_KANGAROO_JUMPS);
+    memcpy(f.js.data(), &b[112], 512);
+    for (uint32_t j = 0; j < BSGS_KANGAROO_JUMPS; j++) if (!f.js[j]) return path + ": jump scalar " + std::to_string(j) + " is zero";
+    f.x.resize(T); f.d.resize(T);
+    for (uint64_t i = 0; i < T; i++) {
+        memcpy(&f.x[i], &b[TAMES_HEADER + TAMES_ENTRY * i], 8); memcpy(&f.d[i], &b[TAMES_HEADER + TAMES_ENTRY * i + 8], 16);
+        if (i && f.x[i] <= f.x[i - 1]) return path + ": entries are not strictly ascending (entry " + std::to_string(i) + ")";
+    }
+    return "";
+}
+
+// the planning defaults ("tame table"): K = T 2^dp trail points stand for the table; m = W / 2K keeps the tame trails from saturating the
+// range; tame starts reach E = max(4 m W / K, W / 8) past the range; wild starts are spread over U = min(2^32, W / 4, E); a wild kangaroo older than A steps starts afresh
+struct TamesPlan { uint64_t m, A; u128 E, U; double per_key; };
+TamesPlan tames_plan(u128 W, uint64_t T, uint32_t dp)
+{
+    TamesPlan t;
+    const long double K = (long double)T * std::ldexp(1.0L, (int)dp), w = (long double)W;
+    const long double m = std::min(std::ldexp(1.0L, 62) - 1.0L, std::max(2.0L, w / (2.0L * K)));
+    t.m = (uint64_t)m;
+    t.E = std::max((u128)std::min(std::ldexp(1.0L, 126), std::max(1.0L, 4.0L * m * w / K)), W / 8);
+    t.U = std::min(std::min<u128>((u128)1 << 32, std::max<u128>(W / 4, 1)), t.E);   // (within E: a wild start beyond the tame starts meets no trail)
+    t.per_key = (double)(w / K);
+    t.A = (uint64_t)std::min(std::ldexp(1.0L, 62), 8.0L * (w / K + std::ldexp(1.0L, (int)dp)));
+    return t;
+}
+
+std::string u128_hex(u128 v) { return hs::fe_to_hex(hs::sc_from_u128(v)); }
+
+// ---- the search rule without a device -------------------------------------------------------------------------------------------------------------------
+class TamesRule {
+public:
+    enum What { FOUND, FALSE_MATCH, STALE, RESEED };
+    struct Event { What what; uint32_t a; Scalar key; };
+    TamesRule(const TamesFile &f, u128 W, const std::vector<Affine> &P, const std::vector<bool> &presolved, uint64_t n_wild, uint64_t age_launches)
+        : f_(f), W_(W), P_(P), known_(presolved), key_(P.size()), asg_((uint32_t)P.size(), presolved, n_wild), age_(n_wild, 0), limit_(age_launches)
+    {
+        for (size_t k = 0; k < P.size(); k++) { if (presolved[k]) { key_[k] = f.lo; solved_++; } same_[hs::compress_pubkey(P[k])].push_back((uint32_t)k); }
+    }
+    bool known(uint32_t k) const { return known_[k]; }
+    const Scalar &key(uint32_t k) const { return key_[k]; }
+    uint32_t solved() const { return solved_; }
+    uint32_t key_of(uint64_t w) const { return asg_.key(w); }
+    const std::vector<uint32_t> &keys() const { return asg_.keys(); }
+    uint64_t matches() const { return matches_; }
+    uint64_t false_matches() const { return false_; }
+    uint64_t reseeds() const { return reseeds_; }
+    // one record the device handed back: flags and offset of the kangaroo, reserved = entry number + 1 or 0
+    void record(uint32_t flags, uint32_t reserved, i128 d, std::vector<Event> &ev)
+    {
+        if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; ev.push_back(Event{RESEED, 0, Scalar()}); return; }
+        if (!reserved || reserved > f_.x.size()) return;               // (the device hands back nothing else)
+        matches_++;
+        const uint32_t k = (flags >> BSGS_KANGAROO_KEY_SHIFT) & 0xFFFFu;
+        if (k >= P_.size() || known_[k]) { ev.push_back(Event{STALE, k, Scalar()}); return; }
+        const i128 off = f_.d[reserved - 1] - d;                       // k' = d_T - d_W
+        Scalar cand;
+        if (off >= 0 && (u128)off < W_) {
+            cand = hs::sc_add(f_.lo, hs::sc_from_u128((u128)off));
+            const Affine q = hs::point_mul(hs::G, cand);
+            if (!q.inf && hs::fe_equal(q.x, P_[k].x) && hs::fe_equal(q.y, P_[k].y)) {
+                for (uint32_t o : same_[hs::compress_pubkey(P_[k])]) if (!known_[o]) {       // equal points of the list are solved with it
+                    known_[o] = true; key_[o] = cand; solved_++; asg_.solved(o);
+                    ev.push_back(Event{FOUND, o, cand});
+                }
+                return;
+            }
+        }
+        false_++;
+        ev.push_back(Event{FALSE_MATCH, k, Scalar()});
+    }
+    // a launch of wild kangaroos [first, first + n) ended: those that have walked more than the limit since their start are named
+    void launch_done(uint64_t first, uint64_t n, std::vector<uint64_t> &aged)
+    {
+        for (uint64_t w = first; w < first + n; w++) if (++age_[w] > limit_) { aged.push_back(w); reseeds_++; }
+    }
+    // wild kangaroo w starts afresh: its key from now on (false: no key is open, it rests)
+    bool reseed(uint64_t w, uint32_t *k) { age_[w] = 0; return asg_.reseed(w, *this, k); }
+private:
+    const TamesFile &f_;
+    const u128 W_;
+    const std::vector<Affine> &P_;
+    std::vector<bool> known_;
+    std::vector<Scalar> key_;
+    Assigner asg_;
+    std::vector<uint32_t> age_;
+    const uint64_t limit_;
+    std::map<std::string, std::vector<uint32_t>> same_;
+    uint64_t matches_ = 0, false_ = 0, reseeds_ = 0;
+    uint32_t solved_ = 0;
+};
+
+u128 range_width(const Scalar &lo, const Scalar &hi)
+{
+    const Scalar wm1 = hs::sc_sub(hi, lo);
+    return (((u128)wm1.l[1] << 64) | wm1.l[0]) + 1;
+}
+
+// ---- -ktamesgen ---------------------------------------------------------------------------------------------------------------------------------------
+struct GenMode : Mode {
+    GenMode(const KangConfig &c, const Prologue &p) : c(c), T(c.ktn)
+    {
+        saves = false;
+        // dp: the command line's, else about (log2(W / T)) / 2 - 4: the trails stay a small part of the range while a wild walk to the next DP stays short
+        dp_fixed = c.dp >= 0 ? c.dp : (int)std::max(0.0, std::min(14.0, std::floor(std::log2((double)p.W / (double)T) / 2.0) - 4.0));
+        plan = tames_plan(p.W, T, (uint32_t)dp_fixed);
+        mean_jump = (double)plan.m;
+        expected = 2.0 * (double)T * std::ldexp(1.0, dp_fixed);
+        herd_label = "herd (GPU, all tame), engine ";
+        span = p.W + plan.E - 1;
+        map.reserve((size_t)T * 2);
+    }
+    std::string fingerprint(const Prologue &, const WorkHeader &) const override { return ""; }
+    bool before_devices(Prologue &p) override { pro = &p; p.t0 = Clock::now(); return true; }
+    const char *setup(bsgs_dev *dev) override
+    {
+        const Plan &pl = pro->pl;
+        return bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) == BSGS_OK ? nullptr : "bsgs_kangaroo_setup";
+    }
+    // every kangaroo is tame: t uniform in [1, W + E), d = t
+    const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) override
+    {
+        const size_t n = idx.empty() ? (size_t)pro->pl.kn : idx.size();
+        std::vector<i128> d(n);
+        std::vector<uint32_t> fl(n, 0u);
+        { std::lock_guard<std::mutex> lk(sh.rng_m); for (size_t k = 0; k < n; k++) d[k] = (i128)(1 + draw128(sh.rng) % span); }
+        uint32_t ninf = 0, first = 0;
+        if (bsgs_kangaroo_seed(dev, nullptr, idx.empty() ? nullptr : idx.data(), 0, (uint32_t)n, (const uint8_t *)d.data(), fl.data(), &ninf, &first) != BSGS_OK) return "bsgs_kangaroo_seed";
+        if (ninf) sh.push_reseed(e, idx.empty() ? first : idx[first]);
+        return nullptr;
+    }
+    bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &sh) override
+    {
+        if (map.size() >= T) return false;
+        if (r.flags & BSGS_KANGAROO_DEAD) { sh.push_reseed(e, r.kangaroo); return true; }
+        uint64_t x; i128 d;
+        memcpy(&x, r.x, 8); memcpy(&d, r.d, 16);
+        if (!map.emplace(x, d).second) { merges++; sh.push_reseed(e, r.kangaroo); return true; }     // it has merged into a known trail
+        if (map.size() >= T) { sh.stop = true; return false; }
+        return true;
+    }
+    uint32_t entry_flags(uint32_t) const override { return 0u; }
+    bool done() const override { return map.size() >= T; }
+    bool give_up(uint64_t steps) override { return (double)steps > 50.0 * pro->pl.expected; }
+    void status(double rate, uint64_t st, uint64_t dps) const override
+    {
+        printf("\r[%u] %.3e steps/s  steps 2^%.2f  entries %zu of %llu  DPs %llu  merges %llu  %.0fs   ", pro->pl.engines, rate, st ? std::log2((double)st) : 0.0, map.size(),
+               (unsigned long long)T, (unsigned long long)dps, (unsigned long long)merges, since(pro->t0));
+    }
+    const WorkKeys *save(WorkHeader &, std::vector<uint8_t> &) override { return nullptr; }
+
+    const KangConfig &c;
+    const uint64_t T;
+    const Prologue *pro = nullptr;
+    TamesPlan plan;
+    u128 span;
+    std::unordered_map<uint64_t, i128> map;
+    uint64_t merges = 0;
+};
+
+int tames_generate(const KangConfig &c)
+{
+    Prologue p(c);
+    printf("Kangaroo range [%s, %s], width 2^%.2f: a tame table of %llu entries\n", hs::fe_to_hex(p.lo).c_str(), hs::fe_to_hex(p.hi).c_str(), std::log2((double)p.W),
+           (unsigned long long)c.ktn);
+    GenMode mode(c, p);
+    p.complete(c, mode);
+    printf("Plan: mean jump m = %llu, tame starts reach E = 0x%s past the range, -dp %u\n", (unsigned long long)mode.plan.m, u128_hex(mode.plan.E).c_str(), p.pl.dp);
+    Shared sh(p);
+    const Outcome o = run(c, p, sh, mode);
+    const double secs = since(p.t0);
+    if (o != DONE) {
+        printf("\nKangaroo: tame table not finished after %llu steps (%s), %zu of %llu entries; nothing written\n", (unsigned long long)sh.steps.load(),
+               o == GAVE_UP ? "the trails have saturated the range: a smaller -ktn or -dp" : o == BUDGET ? "-ksteps" : "signal", mode.map.size(), (unsigned long long)c.ktn);
+        return o == GAVE_UP ? 1 : 3;
+    }
+    TamesFile f;
+    f.dp = p.pl.dp; f.lo = p.lo; f.hi = p.hi; f.steps = sh.steps.load(); f.seed = p.wh.seed; f.m = mode.plan.m; f.js = p.js;
+    std::vector<std::pair<uint64_t, i128>> en(mode.map.begin(), mode.map.end());
+    std::sort(en.begin(), en.end());
+    en.resize((size_t)c.ktn);
+    for (const auto &kv : en) { f.x.push_back(kv.first); f.d.push_back(kv.second); }
+    std::string path = c.ktamesgen;
+    if (path.find('/') == std::string::npos) path = c.dir + "/" + path;
+    if (!write_tames(path, f)) die("cannot write " + path);
+    printf("\nTame table %s: %llu entries, %.3e steps, %llu DPs, %llu merges, %.2fs\n", path.c_str(), (unsigned long long)c.ktn, (double)f.steps, (unsigned long long)sh.dps.load(),
+           (unsigned long long)mode.merges, secs);
+    fflush(stdout);
+    return 0;
+}
+
+// ---- -ktames --------------------------------------------------------------------------------------------------------------------------------------------
+struct SearchMode : Mode {
+    SearchMode(const KangConfig &c, const std::vector<Affine> &P, const TamesFile &f, const Prologue &p) : c(c), P(P), L((uint32_t)P.size()), f(f)
+    {
+        saves = false;
+        dp_fixed = (int)f.dp;
+        mean_jump = (double)f.m;
+        jump_scalars = f.js.data();                                    // the search walks with exactly the generator's jumps
+        plan = tames_plan(p.W, f.x.size(), f.dp);
+        herd_label = "herd (GPU, all wild), engine ";
+    }
+    std::string fingerprint(const Prologue &, const WorkHeader &) const override { return ""; }
+    void report(uint32_t k, const Scalar &key)
+    {
+        std::string console;
+        const std::string win = key_lines((int)k + 1, key, P[k], console);
+        fputs(console.c_str(), stdout);
+        fflush(stdout);
+        std::ofstream o(c.dir + "/win.txt", std::ios::app | std::ios::binary);
+        o << win;
+        found_n++;
+    }
+    bool before_devices(Prologue &p) override
+    {
+        pro = &p;
+        { Config rc; rc.dir = c.dir; read_recovery(rc); }             // (win.txt starts empty, as on the BSGS path)
+        p.t0 = Clock::now();
+        const Affine naG = hs::affine_neg(hs::point_mul(hs::G, p.lo));
+        presolved.assign(L, false);
+        qxy.resize(64 * (size_t)L);
+        for (uint32_t k = 0; k < L; k++) {                             // Q_k = P_k - a*G; a key equal to a*G is solved here and keeps its slot
+            Affine Q = hs::point_add(P[k], naG);
+            if (Q.inf) { presolved[k] = true; report(k, p.lo); Q = hs::G; }
+            hs::affine_to_le(Q, &qxy[64 * (size_t)k], &qxy[64 * (size_t)k + 32]);
+        }
+        open0 = L - (uint32_t)found_n;
+        expected = (double)open0 * plan.per_key;
+        if (!open0) printf("Found %d of %u\n", found_n, L);
+        return open0 != 0;
+    }
+    void prepare(Prologue &p, Shared &s)
+    {
+        const Plan &pl = p.pl;
+        // (the give-up bound's allowance per kangaroo: the way to the next DP, and W / K steps before it meets a trail at all -- the trails of a small
+        // generating herd leave gaps that long)
+        overhead = (double)pl.kn * pl.engines * (plan.per_key + std::ldexp(1.0, (int)pl.dp));
+        const uint64_t launches = std::max<uint64_t>(1, (plan.A + pl.S - 1) / pl.S);
+        rule.reset(new TamesRule(f, p.W, P, presolved, pl.kn * pl.engines, launches));
+        printf("Tame table: %zu entries at -dp %u, mean jump %llu; about 2^%.2f steps per key; a wild kangaroo starts afresh after %llu launches\n", f.x.size(), f.dp,
+               (unsigned long long)f.m, std::log2(plan.per_key + std::ldexp(1.0, (int)f.dp)), (unsigned long long)launches);
+        off0.resize(pl.engines);
+        for (uint32_t e = 0; e < pl.engines; e++) { off0[e].resize(pl.kn); for (uint64_t i = 0; i < pl.kn; i++) off0[e][i] = (i128)(draw128(s.rng) % plan.U); }
+        last_solved = rule->solved();
+    }
+    const char *setup(bsgs_dev *dev) override
+    {
+        const Plan &pl = pro->pl;
+        if (bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup";
+        if (bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) return "bsgs_kangaroo_set_keys";
+        return bsgs_kangaroo_tames_install(dev, f.x.data(), f.x.size()) == BSGS_OK ? nullptr : "bsgs_kangaroo_tames_install";
+    }
+    // every kangaroo is wild: kangaroo of key k at Q_k + u*G, u uniform in [0, U), flags WILD | k << 8
+    const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &s) override
+    {
+        const uint64_t kn = pro->pl.kn, w0 = (uint64_t)e * kn;
+        std::vector<uint32_t> use, fl, key;
+        std::vector<i128> d;
+        if (idx.empty()) {
+            fl.assign(kn, BSGS_KANGAROO_WILD); key.resize(kn);
+            for (uint64_t i = 0; i < kn; i++) key[i] = rule->key_of(w0 + i);
+            d.swap(off0[e]);
+        } else {
+            std::lock_guard<std::mutex> lt(s.tab_m);
+            std::lock_guard<std::mutex> lk(s.rng_m);
+            for (uint32_t i : idx) {
+                uint32_t k = 0;
+                if (!rule->reseed(w0 + i, &k)) continue;               // no key is open: the kangaroo rests
+                use.push_back(i); fl.push_back(BSGS_KANGAROO_WILD); key.push_back(k);
+                d.push_back((i128)(draw128(s.rng) % plan.U));
+            }
+            if (use.empty()) return nullptr;
+        }
+        uint32_t ninf = 0, first = 0;
+        if (bsgs_kangaroo_seed_keys(dev, use.empty() ? nullptr : use.data(), 0, (uint32_t)d.size(), (const uint8_t *)d.data(), fl.data(), key.data(), &ninf, &first) != BSGS_OK)
+            return "bsgs_kangaroo_seed_keys";
+        if (ninf) s.push_reseed(e, use.empty() ? first : use[first]);  // Q_k + u*G at infinity names a key below the range: the kangaroo starts again
+        return nullptr;
+    }
+    // the launch, the match on the device, the matched and DEAD records alone; then the kangaroos that have walked too long
+    int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &s) override
+    {
+        uint64_t n_seen = 0;
+        const int rc = bsgs_kangaroo_run_tames(dev, steps, recs, cap, n, &n_seen, dropped, nullptr);
+        if (rc != BSGS_OK) return rc;
+        seen += n_seen;
+        std::vector<uint64_t> aged;
+        const uint64_t kn = pro->pl.kn;
+        { std::lock_guard<std::mutex> lt(s.tab_m); rule->launch_done((uint64_t)e * kn, kn, aged); }
+        for (uint64_t w : aged) s.push_reseed(e, (uint32_t)(w - (uint64_t)e * kn));
+        return rc;
+    }
+    bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &s) override
+    {
+        std::vector<TamesRule::Event> ev;
+        i128 d;
+        memcpy(&d, r.d, 16);
+        rule->record(r.flags, r.reserved, d, ev);
+        const uint64_t kn = pro->pl.kn;
+        for (const TamesRule::Event &x : ev) {
+            if (x.what == TamesRule::RESEED) s.push_reseed(e, r.kangaroo);
+            if (x.what != TamesRule::FOUND) continue;
+            report(x.a, x.key);
+            for (uint64_t w = 0; w < rule->keys().size(); w++) if (rule->keys()[w] == x.a) s.push_reseed((uint32_t)(w / kn), (uint32_t)(w % kn));
+        }
+        if (rule->solved() == L) s.stop = true;
+        return true;
+    }
+    uint32_t entry_flags(uint32_t) const override { return 0u; }
+    bool done() const override { return rule && rule->solved() == L; }
+    bool give_up(uint64_t steps) override
+    {
+        const uint32_t now = rule->solved();
+        if (now != last_solved) { last_solved = now; steps_mark = steps; }
+        return (double)(steps - steps_mark) > 20.0 * ((double)(L - now) * plan.per_key + overhead);
+    }
+    void status(double rate, uint64_t st, uint64_t) const override
+    {
+        printf("\r[%u] %.3e steps/s  steps 2^%.2f  solved %u/%u  records seen %llu  matches %llu  %.0fs   ", pro->pl.engines, rate, st ? std::log2((double)st) : 0.0, rule->solved(), L,
+               (unsigned long long)seen.load(), (unsigned long long)rule->matches(), since(pro->t0));
+    }
+    const WorkKeys *save(WorkHeader &, std::vector<uint8_t> &) override { return nullptr; }
+
+    const KangConfig &c;
+    const std::vector<Affine> &P;
+    const uint32_t L;
+    const TamesFile &f;
+    const Prologue *pro = nullptr;
+    TamesPlan plan;
+    std::unique_ptr<TamesRule> rule;
+    std::vector<bool> presolved;
+    std::vector<uint8_t> qxy;
+    std::vector<std::vector<i128>> off0;
+    std::atomic<uint64_t> seen{0};
+    int found_n = 0;
+    uint32_t open0 = 0, last_solved = 0;
+    uint64_t steps_mark = 0;
+    double overhead = 0.0;
+};
+
+// every entry of the table against d*G on the first engine's device (bsgs_kangaroo_verify_points, tame flags), 2^20 at a time, before anything walks
+void tames_verify(const TamesFile &f, int gpu)
+{
+    const auto ts = Clock::now();
+    bsgs_dev *dev = nullptr;
+    CK(bsgs_dev_open(gpu, &dev));
+    std::vector<uint8_t> jxy(64 * (size_t)BSGS_KANGAROO_JUMPS);
+    for (uint32_t j = 0; j < BSGS_KANGAROO_JUMPS; j++) hs::affine_to_le(hs::G, &jxy[64 * (size_t)j], &jxy[64 * (size_t)j + 32]);
+    CK(bsgs_kangaroo_setup(dev, jxy.data(), f.js.data(), f.dp, 64, 1, 64));      // the smallest herd: the verification's comb hangs on one
+    uint8_t g[64];
+    hs::affine_to_le(hs::G, g, g + 32);
+    const uint64_t T = f.x.size(), step = 1u << 20;
+    std::vector<uint32_t> fl((size_t)std::min(T, step), 0u);
+    for (uint64_t pos = 0; pos < T; pos += step) {
+        const uint32_t m = (uint32_t)std::min(T - pos, step);
+        uint32_t n_bad = 0, first = 0;
+        CK(bsgs_kangaroo_verify_points(dev, g, m, (const uint8_t *)&f.d[pos], fl.data(), &f.x[pos], &n_bad, &first, 1));
+        if (n_bad) { bsgs_dev_close(dev); die("Tame table is damaged: entry " + std::to_string(pos + first) + " does not match its offset"); }
+    }
+    bsgs_dev_close(dev);
+    printf("[verify] tame table: %llu entries %.3fs\n", (unsigned long long)T, since(ts));
+}
+
+int tames_search(const KangConfig &c)
+{
+    // the table is read before any device is looked for
+    TamesFile f;
+    std::string path = c.ktames;
+    { struct stat sb; if (stat(path.c_str(), &sb) != 0 && stat((c.dir + "/" + path).c_str(), &sb) == 0) path = c.dir + "/" + path; }
+    const std::string bad = read_tames(path, f);
+    if (!bad.empty()) die("-ktames: " + bad);
+    std::vector<std::string> pub_hex;
+    if (!c.infile.empty()) { Config fc; fc.infile = c.infile; pub_hex = read_pubs(fc); if (pub_hex.empty()) die("No public keys in " + c.infile); }
+    else pub_hex.push_back(c.pub);
+    if (pub_hex.size() > BSGS_KANGAROO_MAX_KEYS) die("-kangaroo -ktames: at most 65535 public keys, the file has " + std::to_string(pub_hex.size()));
+    const uint32_t L = (uint32_t)pub_hex.size();
+    std::vector<Affine> P(L);
+    for (uint32_t k = 0; k < L; k++) if (!hs::parse_pubkey(P[k], pub_hex[k]) || !hs::on_curve(P[k])) die("Invalid Public Key (line " + std::to_string(k + 1) + ") length!!!");
+    Prologue p(c);
+    if (hs::fe_cmp(p.lo, f.lo) != 0 || hs::fe_cmp(p.hi, f.hi) != 0) die("Tame table was made for another range");
+    printf("Kangaroo range [%s, %s], width 2^%.2f, %u public key(s), tame table %s\n", hs::fe_to_hex(p.lo).c_str(), hs::fe_to_hex(p.hi).c_str(), std::log2((double)p.W), L, path.c_str());
+    SearchMode mode(c, P, f, p);
+    p.complete(c, mode);
+    if (!p.go) return 0;
+    if (c.verify) tames_verify(f, p.gpus[0]);
+    Shared sh(p);
+    mode.prepare(p, sh);
+    const Outcome o = run(c, p, sh, mode);
+    const TamesRule &r = *mode.rule;
+    if (o == GAVE_UP) printf("\nKangaroo: %u of %u keys open after 20 times the expected steps (are the keys in the range?)\n", L - r.solved(), L);
+    else if (o != DONE) printf("\nKangaroo: stopped after %llu steps (%s), %u of %u keys open\n", (unsigned long long)sh.steps.load(), o == BUDGET ? "-ksteps" : "signal", L - r.solved(), L);
+    printf("Job time %.2fs, %.3e kangaroo steps, %llu records seen (%llu dropped), %llu matches, %llu false matches, %llu re-seeds\n", since(p.t0), (double)sh.steps.load(),
+           (unsigned long long)mode.seen.load(), (unsigned long long)sh.dropped.load(), (unsigned long long)r.matches(), (unsigned long long)r.false_matches(), (unsigned long long)r.reseeds());
+    for (uint32_t e = 0; e < p.pl.engines; e++) printf("Engine %u (GPU #%d): %llu records\n", e, p.gpus[e], (unsigned long long)sh.engine_records[e]);
+    printf("Found %d of %u\n", mode.found_n, L);
+    fflush(stdout);
+    return o == DONE ? 0 : (o == BUDGET || o == INTERRUPTED) ? 3 : 1;
+}
+}  // namespace
+
+int kangaroo_tames_main(const KangConfig &c) { return c.ktamesgen.empty() ? tames_search(c) : tames_generate(c); }
+
+// -selftest kangaroo-tames FILE [pk pke]: the header fields of a tame table, its ordering, and with a range whether it is the table's
+int kangaroo_tames_selftest(const std::vector<std::string> &a)
+{
+    if (a.size() != 1 && a.size() != 3) return 2;
+    TamesFile f;
+    const std::string bad = read_tames(a[0], f);
+    if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
+    printf("version %u\ndp %u\npk %s\npke %s\nentries %zu\nsteps %llu\nseed 0x%llx\nmean jump %llu\n", TAMES_VERSION, f.dp, hs::fe_to_hex(f.lo).c_str(), hs::fe_to_hex(f.hi).c_str(), f.x.size(),
+           (unsigned long long)f.steps, (unsigned long long)f.seed, (unsigned long long)f.m);
+    if (a.size() == 3) {
+        Scalar lo, hi;
+        if (!hs::fe_from_hex(lo, cut_hex(a[1])) || !hs::fe_from_hex(hi, cut_hex(a[2]))) return 2;
+        if (hs::fe_cmp(lo, f.lo) != 0 || hs::fe_cmp(hi, f.hi) != 0) { fprintf(stderr, "Tame table was made for another range\n"); return 1; }
+    }
+    printf("ok\n");
+    return 0;
+}
+
+// -selftest kangaroo-tames-image: tags (decimal or 0x..., white space between them) from stdin -> "lines <n>" and the SHA-1 of the image
+int kangaroo_tames_image_selftest(const std::vector<std::string> &)
+{
+    std::vector<uint64_t> tags;
+    std::string tok;
+    while (std::cin >> tok) tags.push_back(strtoull(tok.c_str(), nullptr, 0));
+    uint64_t lines = 0;
+    if (bsgs_kangaroo_tames_image(tags.data(), tags.size(), nullptr, 0, &lines) != BSGS_OK) { fprintf(stderr, "%s\n", bsgs_last_error()); return 1; }
+    std::string image((size_t)lines * 64, '\0');
+    if (bsgs_kangaroo_tames_image(tags.data(), tags.size(), &image[0], image.size(), &lines) != BSGS_OK) { fprintf(stderr, "%s\n", bsgs_last_error()); return 1; }
+    printf("lines %llu\ndigest %s\n", (unsigned long long)lines, sha1_hex(image).c_str());
+    return 0;
+}
+
+// -selftest kangaroo-tames-search FILE <pubkey>[,<pubkey>...] <wild kangaroos> <launches before a kangaroo is aged> <item>...: the search rule on a script.
+//   R,<x hex>,<d hex: 128-bit two's complement>,<kangaroo>   a record of wild kangaroo <kangaroo>; the table is looked up as the device does, by the low 64 bits
+//   D,<kangaroo>                                             its DEAD record
+//   L                                                        a launch of every kangaroo has ended
+// One line per event: "miss", "found <k> <key hex>", "false", "stale", "reseed <kangaroo> <key>", "aged <kangaroo> <key>", and after a found key, for each of
+// its kangaroos in ascending order, "reassign <kangaroo> <key>" ("rest <kangaroo>" when no key is open); then "summary <matches> <false matches> <re-seeds> <solved>".
+int kangaroo_tames_search_selftest(const std::vector<std::string> &a)
+{
+    if (a.size() < 4) return 2;
+    TamesFile f;
+    const std::string bad = read_tames(a[0], f);
+    if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
+    std::vector<Affine> P;
+    if (!parse_pubs(a[1], P) || P.empty() || P.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
+    const uint64_t n_wild = strtoull(a[2].c_str(), nullptr, 10), limit = strtoull(a[3].c_str(), nullptr, 10);
+    if (!n_wild || n_wild > (1u << 20)) return 2;
+    const Affine aG = hs::point_mul(hs::G, f.lo);
+    std::vector<bool> presolved(P.size(), false);
+    bool open = false;
+    for (size_t k = 0; k < P.size(); k++) {
+        presolved[k] = hs::fe_equal(P[k].x, aG.x) && hs::fe_equal(P[k].y, aG.y);
+        if (presolved[k]) printf("presolved %zu\n", k); else open = true;
+    }
+    if (!open) { printf("summary 0 0 0 %zu\n", P.size()); return 0; }
+    TamesRule rule(f, range_width(f.lo, f.hi), P, presolved, n_wild, limit);
+    auto start_afresh = [&](const char *word, uint64_t w) {
+        uint32_t k = 0;
+        if (rule.reseed(w, &k)) printf("%s %llu %u\n", word, (unsigned long long)w, k); else printf("rest %llu\n", (unsigned long long)w);
+    };
+    for (size_t i = 4; i < a.size(); i++) {
+        const std::vector<std::string> t = split_commas(a[i]);
+        std::vector<TamesRule::Event> ev;
+        uint64_t w = 0;
+        if (t.size() == 1 && t[0] == "L") {
+            std::vector<uint64_t> aged;
+            rule.launch_done(0, n_wild, aged);
+            for (uint64_t v : aged) start_afresh("aged", v);
+            continue;
+        } else if (t.size() == 2 && t[0] == "D") {
+            w = strtoull(t[1].c_str(), nullptr, 10);
+            if (w >= n_wild) return 2;
+            rule.record(BSGS_KANGAROO_WILD | BSGS_KANGAROO_DEAD | rule.key_of(w) << BSGS_KANGAROO_KEY_SHIFT, 0, 0, ev);
+        } else if (t.size() == 4 && t[0] == "R") {
+            Scalar x, dd;
+            if (!hs::fe_from_hex(x, t[1]) || !hs::fe_from_hex(dd, t[2]) || dd.l[2] || dd.l[3]) return 2;
+            w = strtoull(t[3].c_str(), nullptr, 10);
+            if (w >= n_wild) return 2;
+            const auto it = std::lower_bound(f.x.begin(), f.x.end(), x.l[0]);
+            if (it == f.x.end() || *it != x.l[0]) { printf("miss\n"); continue; }
+            rule.record(BSGS_KANGAROO_WILD | rule.key_of(w) << BSGS_KANGAROO_KEY_SHIFT, (uint32_t)(it - f.x.begin()) + 1u, (i128)(((u128)dd.l[1] << 64) | dd.l[0]), ev);
+        } else return 2;
+        for (const TamesRule::Event &e : ev) switch (e.what) {
+            case TamesRule::FALSE_MATCH: printf("false\n"); break;
+            case TamesRule::STALE: printf("stale\n"); break;
+            case TamesRule::RESEED: start_afresh("reseed", w); break;
+            case TamesRule::FOUND: {
+                printf("found %u %s\n", e.a, hs::fe_to_hex(e.key).c_str());
+                const std::vector<uint32_t> before = rule.keys();
+                for (uint64_t v = 0; v < before.size(); v++) if (before[v] == e.a) start_afresh("reassign", v);
+                break;
+            }
+        }
+    }
+    printf("summary %llu %llu %llu %u\n", (unsigned long long)rule.matches(), (unsigned long long)rule.false_matches(), (unsigned long long)rule.reseeds(), rule.solved());
+    return 0;
+}

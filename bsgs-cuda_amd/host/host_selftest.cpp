@@ -147,6 +147,12 @@ int selftest(int argc, char **argv)
             return kangaroo_symlist_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-symlist") {                            // the same table on a scripted record stream (host_kangaroo_symlist.cpp)
             return kangaroo_symlist_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-tames-image") {                        // the device image of a tame table (host_kangaroo_tames.cpp; no GPU)
+            return kangaroo_tames_image_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-tames-search") {                       // the search rule of -ktames on scripted records
+            return kangaroo_tames_search_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-tames") {                              // the header of a tame table file
+            return kangaroo_tames_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-multi-roundtrip") {                    // the same through a version-3 work file in the middle of the stream
             return kangaroo_multi_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-multi") {                              // the table for a list of keys on a scripted record stream (host_kangaroo_multi.cpp)

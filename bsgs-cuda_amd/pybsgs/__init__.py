@@ -29,6 +29,7 @@ NATIVE_SYMBOLS = [
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
     "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym", "bsgs_kangaroo_setup_sym_keys",
     "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_kangaroo_verify", "bsgs_kangaroo_verify_points", "bsgs_selftest_fe3",
+    "bsgs_kangaroo_tames_image", "bsgs_kangaroo_tames_install", "bsgs_kangaroo_run_tames",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
@@ -190,6 +191,9 @@ def lib():
             "bsgs_kangaroo_verify": [vp, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32],
             "bsgs_kangaroo_verify_points": [vp, u8p, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32],
             "bsgs_kangaroo_seed": [vp, u8p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+            "bsgs_kangaroo_tames_image": [C.POINTER(C.c_uint64), C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)],
+            "bsgs_kangaroo_tames_install": [vp, C.POINTER(C.c_uint64), C.c_uint64],
+            "bsgs_kangaroo_run_tames": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
         }
         for name, args in sig.items():
             fn = getattr(L, name, None)
@@ -209,6 +213,18 @@ def _chk(rc, allow_overflow=False):
 
 def le32(v):
     return int(v).to_bytes(32, "little")
+
+
+def kangaroo_tames_image(tags):
+    """the device image of a tame table (include/bsgs_hip.h, "Kangaroo, tame table") from its tags, the low 64 bits of x in entry order: (bytes, lines).
+    Needs no device; a tag that occurs twice raises"""
+    n = len(tags)
+    arr = (C.c_uint64 * max(1, n))(*tags)
+    lines = C.c_uint64()
+    _chk(lib().bsgs_kangaroo_tames_image(arr, n, None, 0, C.byref(lines)))
+    buf = C.create_string_buffer(lines.value * 64)
+    _chk(lib().bsgs_kangaroo_tames_image(arr, n, buf, len(buf), C.byref(lines)))
+    return buf.raw, lines.value
 
 
 def build_info():
@@ -282,6 +298,7 @@ class Device:
         _chk(lib().bsgs_dev_open(device_id, C.byref(self.h)))
         self.L = lib()
         self._kang_keyed = False               # the herd is one of kangaroo_setup_sym_keys: states carry a key
+        self._kang_cap = 0                     # record capacity of the herd (kangaroo_setup*)
 
     def close(self):
         if self.h:
@@ -709,6 +726,23 @@ class Device:
         out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step, "key": r.reserved}
                for r in recs[:n.value]]
         return out, dropped.value, ms.value
+
+    def kangaroo_tames_install(self, tags):
+        """the tame table of the herd: tags = the low 64 bits of x of its entries, pairwise different, in entry order; replaces an earlier table and lives
+        as long as the herd (kangaroo_setup, kangaroo_setup_sym)"""
+        _chk(self.L.bsgs_kangaroo_tames_install(self.h, (C.c_uint64 * max(1, len(tags)))(*tags), len(tags)))
+
+    def kangaroo_run_tames(self, steps):
+        """one launch of `steps` steps matched against the tame table on the device: (records, n_seen, dropped, kernel ms).  Only the records whose x is in
+        the table and the DEAD ones come back, as kangaroo_run's plus "entry": the table entry's number, None for a DEAD record that matched nothing;
+        n_seen = the records the walk produced"""
+        cap = max(1, self._kang_cap)
+        recs = (KangarooRecord * cap)()
+        n, seen, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _chk(self.L.bsgs_kangaroo_run_tames(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(dropped), C.byref(ms)))
+        out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
+                "entry": r.reserved - 1 if r.reserved else None} for r in recs[:n.value]]
+        return out, seen.value, dropped.value, ms.value
 
     def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):
         """start points on the GPU: kangaroo idx[k] (first + k without idx) := (d*G or Q + d*G, d, flags[k]) for d = offsets[k] (a signed integer) and

@@ -2,10 +2,13 @@
 """Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
-    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--out FILE]
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--no-vgprs] [--out FILE]
 
 --sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch); with --keys
 the herd of bsgs_kangaroo_setup_sym_keys, whose kernel entry point reads a kangaroo's key when it writes a record (keys 0..15 dealt out over the herd).
+
+--tames N installs a tame table of N entries (bsgs_kangaroo_tames_install; tags that no record meets, so every lookup ends in a miss, as all but a handful
+do in a search) and times bsgs_kangaroo_run_tames and bsgs_kangaroo_run in turn, launch by launch: the difference of their kernel times is the match.
 
 The starts are 65536 distinct points P0 + i*G, repeated over the herd (the walk's cost does not depend on which point a kangaroo stands on; repeats only
 make their DPs coincide)."""
@@ -51,10 +54,14 @@ def main():
     ap.add_argument("--sym", action="store_true")
     ap.add_argument("--jumps", type=int, default=1024)
     ap.add_argument("--keys", action="store_true")
+    ap.add_argument("--tames", type=int, default=0)
+    ap.add_argument("--no-vgprs", action="store_true", help="do not compile the walk's unit for its VGPR count")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.keys and not a.sym:
         ap.error("--keys goes with --sym")
+    if a.tames and a.keys:
+        ap.error("--tames: the plain herd, or --sym without --keys")
     dev = pybsgs.Device(0)
     L = dev.L
     cus = C.c_int()
@@ -84,6 +91,42 @@ def main():
         pybsgs._chk(L.bsgs_kangaroo_run(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(dropped), C.byref(ms)))
         return ms.value, cnt.value + dropped.value
 
+    if a.tames:
+        import numpy as np
+        t0 = time.perf_counter()
+        tags = np.arange(1, a.tames + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)      # an odd multiplier: pairwise different
+        pybsgs._chk(L.bsgs_kangaroo_tames_install(dev.h, tags.ctypes.data_as(C.POINTER(C.c_uint64)), a.tames))
+        install_s = time.perf_counter() - t0
+        seen = C.c_uint64()
+
+        def launch_tames():
+            pybsgs._chk(L.bsgs_kangaroo_run_tames(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(dropped), C.byref(ms)))
+            return ms.value, seen.value, cnt.value
+
+        for _ in range(a.warmup):
+            launch()
+            launch_tames()
+        plain, both, nrec, back = [], [], 0, 0
+        for _ in range(a.launches):
+            plain.append(launch()[0])
+            k, r, m = launch_tames()
+            both.append(k)
+            nrec += r
+            back += m
+        match = (sum(both) - sum(plain)) / len(both)
+        res = {"what": "kangaroo walk with a tame table matched on the device, one engine, full herd" + (", symmetric walk" if a.sym else ""), "gpu": dev.name(), "kangaroos": n,
+               "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp, "launches": a.launches, "tame_entries": a.tames, "image_bytes": 64 * max(64, 1 << (max(a.tames - 1, 1) // 2).bit_length()),
+               "install_s": install_s, "ms_per_launch_walk": sum(plain) / len(plain), "ms_per_launch_walk_and_match": sum(both) / len(both), "ms_match": match,
+               "match_share": match / (sum(both) / len(both)), "records_per_launch": nrec / a.launches, "records_returned_per_launch": back / a.launches,
+               "steps_per_s_kernel_walk": n * a.steps / (sum(plain) / len(plain) / 1e3), "steps_per_s_kernel_walk_and_match": n * a.steps / (sum(both) / len(both) / 1e3)}
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        dev.close()
+        return
+
     for _ in range(a.warmup):
         launch()
     kms, nrec = [], 0
@@ -98,7 +141,7 @@ def main():
     res = {"what": "kangaroo walk rate, one engine, full herd" + (", symmetric walk, %d jump points" % a.jumps if a.sym else "") + (", a key per kangaroo" if a.keys else ""), "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp,
            "launches": a.launches, "steps_per_s": steps / wall, "steps_per_s_kernel": steps / (sum(kms) / 1e3), "ms_per_launch": sum(kms) / len(kms),
            "ms_per_launch_min": min(kms), "bytes_per_step": bps, "hbm_GBps_implied": steps * bps / (sum(kms) / 1e3) / 1e9,
-           "records_per_launch": nrec / a.launches, "vgprs": vgprs(a.sym, a.keys)}
+           "records_per_launch": nrec / a.launches, "vgprs": None if a.no_vgprs else vgprs(a.sym, a.keys)}
     line = json.dumps(res)
     print(line)
     if a.out:
