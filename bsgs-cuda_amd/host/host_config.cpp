@@ -85,7 +85,9 @@ void usage(const Config &c)
            "-ktamesgen F Kangaroo: make a tame table of -ktn T distinguished points of the range [-pk, -pke] and write it to F (nothing else is saved; no -wl, -wt)\n"
            "-ktn T       Kangaroo -ktamesgen: entries of the table, 1..2^31\n"
            "-ktames F    Kangaroo: search -pb or every key of -infile with the tame table F of this range: all kangaroos wild, records matched against the table on the GPU\n"
-           "             (the table is verified on the GPU at load, -noverify skips; not with -ksym, -kwalk sym, -wl, -dp; nothing is saved)\n");
+           "             (the table is verified on the GPU at load, -noverify skips; not with -ksym, -kwalk sym, -wl, -dp; nothing is saved)\n"
+           "-kwalk sym   Kangaroo -ktamesgen: the tame table of the symmetric walk (file version 2; with -kjumps, -kjumpscale: default 1024 and 1)\n"
+           "-ktamessym F Kangaroo: as -ktames with a table of the symmetric walk: jump points, scale and scalars come from the file (-ktames refuses such a table, and -kwalk)\n");
 }
 
 Config parse_args(int argc, char **argv)

@@ -247,7 +247,7 @@ const double KSYM_JUMPSCALE = 2.0;                 // DESIGN.md 10, "jump scale"
 KangConfig kang::parse_kangaroo_args(int argc, char **argv)
 {
     KangConfig c;
-    bool ksym = false, kwalk_sym = false, wt_given = false;
+    bool ksym = false, kwalk_sym = false, wt_given = false, ktames_sym = false, ktames_plain = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         for (auto &ch : a) ch = (char)tolower(ch);
@@ -266,7 +266,8 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-wl") c.wl = next();
         else if (a == "-wt") { c.wt = std::max(30, atoi(next().c_str())); wt_given = true; }
         else if (a == "-ktamesgen") c.ktamesgen = next();
-        else if (a == "-ktames") c.ktames = next();
+        else if (a == "-ktames") { c.ktames = next(); ktames_plain = true; }
+        else if (a == "-ktamessym") { c.ktames = next(); ktames_sym = true; }
         else if (a == "-ktn") { c.ktn = strtoull(next().c_str(), nullptr, 0); if (!c.ktn || c.ktn > (1ull << 31)) die("-ktn must be 1..2^31"); }
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
@@ -278,22 +279,26 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-w" || a == "-htsz" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table)");
         else die("Unknown parameter with -kangaroo: " + a);
     }
-    // a tame table (host_kangaroo_tames.cpp): made and used by the plain walk, never saved; every refusal before any device is looked for
+    // a tame table (host_kangaroo_tames.cpp): made by the plain walk, or with -kwalk sym by the symmetric walk (file version 2); searched with -ktames,
+    // a table of the symmetric walk with -ktamessym; never saved; every refusal before any device is looked for
     if (!c.ktamesgen.empty() || !c.ktames.empty()) {
-        const std::string flag = c.ktames.empty() ? "-ktamesgen" : "-ktames";
-        if (!c.ktamesgen.empty() && !c.ktames.empty()) die("-ktamesgen and -ktames exclude each other (make the table first, then search with it)");
-        if (ksym) die("-kangaroo " + flag + " cannot be combined with -ksym (a tame table belongs to the plain walk)");
-        if (kwalk_sym) die("-kangaroo " + flag + " cannot be combined with -kwalk sym (a tame table belongs to the plain walk)");
+        const std::string flag = c.ktames.empty() ? "-ktamesgen" : ktames_sym ? "-ktamessym" : "-ktames";
+        if (ktames_sym && ktames_plain) die("-ktames and -ktamessym exclude each other (one table, made by one walk)");
+        if (!c.ktamesgen.empty() && !c.ktames.empty()) die("-ktamesgen and " + flag + " exclude each other (make the table first, then search with it)");
+        if (ksym) die("-kangaroo " + flag + " cannot be combined with -ksym (-ksym is the search of one key without a table; a tame table of the symmetric walk is made with -ktamesgen -kwalk sym and searched with -ktamessym)");
+        if (kwalk_sym && !c.ktames.empty()) die("-kangaroo " + flag + " cannot be combined with -kwalk sym (the table names its walk: -ktames searches a table of the plain walk, -ktamessym one of the symmetric walk)");
+        c.tames_sym = c.ktames.empty() ? kwalk_sym : ktames_sym;
+        if (ktames_sym && (c.jumps || c.jumpscale != 0.0)) die("-kangaroo -ktamessym takes no -kjumps or -kjumpscale (they belong to -ktamesgen -kwalk sym; the search takes them from the table)");
         if (!c.wl.empty()) die("-kangaroo " + flag + " cannot be combined with -wl (nothing is saved, so nothing is resumed)");
         if (c.ktames.empty()) {
             if (wt_given) die("-kangaroo -ktamesgen cannot be combined with -wt (nothing is saved but the table)");
             if (!c.ktn) die("-kangaroo -ktamesgen needs -ktn (the entries of the table)");
             if (c.pub_given || !c.infile.empty()) die("-kangaroo -ktamesgen takes no -pb or -infile (a tame table serves every key of its range)");
         } else {
-            if (c.dp >= 0) die("-kangaroo -ktames cannot be combined with -dp (the table names its own)");
+            if (c.dp >= 0) die("-kangaroo " + flag + " cannot be combined with -dp (the table names its own)");
             if (c.ktn) die("-ktn belongs to -ktamesgen");
             if (c.pub_given && !c.infile.empty()) die("-kangaroo: -pb and -infile exclude each other (the keys come from the file)");
-            if (!c.pub_given && c.infile.empty()) die("-kangaroo -ktames needs -pb or -infile");
+            if (!c.pub_given && c.infile.empty()) die("-kangaroo " + flag + " needs -pb or -infile");
         }
         return c;
     }

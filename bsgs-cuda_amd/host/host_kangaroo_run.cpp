@@ -87,6 +87,7 @@ void Prologue::complete(const KangConfig &c, Mode &mode)
     pl = plan_herd(sqrtW, (uint32_t)gpus.size(), cus, resume ? (int)wf.h.dp : mode.dp_fixed >= 0 ? mode.dp_fixed : c.dp, c.kn);
     if (resume) { pl.kn = wf.h.herd; pl.G = wf.h.per_thread; }        // the plan of the run that saved, not this GPU's
     if (pl.kn > (1ull << 26)) die("-kn: at most 2^26 kangaroos per engine");
+    mode.planned(*this);
     const double Nk = (double)pl.kn * pl.engines;
     pl.expected = (mode.expected > 0.0 ? mode.expected : 2.0 * sqrtW) + Nk * std::ldexp(1.0, (int)pl.dp);
     pl.S = (uint32_t)std::max(mode.min_launch, std::min(1024.0, pl.expected / Nk / 8.0));

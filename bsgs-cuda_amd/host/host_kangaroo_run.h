@@ -77,6 +77,8 @@ public:
     // between the work file and the devices: the mode's own resume checks ("Recovery file was made with other settings"), its header fields, its first
     // lines, the keys known without a search; false: nothing is left to search
     virtual bool before_devices(Prologue &p) = 0;
+    // once the herd is planned (p.pl: engines, kangaroos, dp) and before the jump table is drawn: a mode whose mean jump depends on the herd sets it here
+    virtual void planned(const Prologue &p) { (void)p; }
     // in an engine's thread; nullptr, or the name of the call that failed
     virtual const char *setup(bsgs_dev *dev) = 0;
     // starts the kangaroos idx of engine e (empty: the whole herd, from the offsets drawn in engine order before the run); draws under the locks it needs

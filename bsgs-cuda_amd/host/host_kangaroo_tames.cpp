@@ -4,6 +4,9 @@
 //   bsgs_mi355x -kangaroo -ktames FILE             an all-wild herd, shared over the keys, walks with the file's jumps; each launch's records are matched
 //                                                 against the table on the device (bsgs_kangaroo_run_tames) and only the matches come back
 // Neither writes kangaroo.work.  TamesRule is the search rule without a device: -selftest kangaroo-tames-search drives it with scripted records.
+// -ktamesgen -kwalk sym and -ktamessym FILE run the symmetric walk (include/bsgs_hip.h "Kangaroo, tame table for the symmetric walk"; tests/kangaroo_tames_sym_model.py): the
+// file is version 2 (R, the jump scale and R scalars), offsets are counted from the middle of the range and are those of representatives, the search's herd is
+// that of bsgs_kangaroo_setup_sym_keys and its records come back through bsgs_kangaroo_run_tames_keys, the entry numbers beside them.
 #include "host_kangaroo_list.h"
 
 #include <iostream>
@@ -12,33 +15,39 @@ namespace {
 using namespace kang;
 
 const char TAMES_MAGIC[9] = "KANGTAME";
-const uint32_t TAMES_VERSION = 1;
-const size_t TAMES_HEADER = 624, TAMES_ENTRY = 24;
+const uint32_t TAMES_VERSION = 1, TAMES_VERSION_SYM = 2;      // 1: the plain walk's table; 2: the symmetric walk's (-kwalk sym): R and the jump scale, R scalars
+const size_t TAMES_FIXED = 112, TAMES_FIXED_SYM = 128, TAMES_ENTRY = 24;
 
 struct TamesFile {
-    uint32_t dp = 0;
+    uint32_t version = TAMES_VERSION, dp = 0;
     Scalar lo, hi;
     uint64_t steps = 0, seed = 0, m = 0;
-    std::vector<uint64_t> js, x;                   // the 64 jump scalars; the entries' low 64 bits of x, strictly ascending
-    std::vector<i128> d;                           // and their offsets
+    uint32_t R = BSGS_KANGAROO_JUMPS;              // version 2: the jump points of the symmetric walk and the scale its mean jump was made with
+    double jumpscale = 1.0;
+    std::vector<uint64_t> js, x;                   // the R jump scalars; the entries' low 64 bits of x, strictly ascending
+    std::vector<i128> d;                           // and their offsets (version 2: of the representative, signed)
+    bool sym() const { return version == TAMES_VERSION_SYM; }
 };
 
 bool write_tames(const std::string &path, const TamesFile &f)
 {
-    std::vector<uint8_t> b(TAMES_HEADER + TAMES_ENTRY * f.x.size(), 0);
+    const size_t head = (f.sym() ? TAMES_FIXED_SYM : TAMES_FIXED) + 8 * (size_t)f.R;
+    std::vector<uint8_t> b(head + TAMES_ENTRY * f.x.size(), 0);
     const uint64_t T = f.x.size();
-    memcpy(&b[0], TAMES_MAGIC, 8); memcpy(&b[8], &TAMES_VERSION, 4); memcpy(&b[12], &f.dp, 4);
+    memcpy(&b[0], TAMES_MAGIC, 8); memcpy(&b[8], &f.version, 4); memcpy(&b[12], &f.dp, 4);
     hs::fe_to_le(f.lo, &b[16]); hs::fe_to_le(f.hi, &b[48]);
     memcpy(&b[80], &T, 8); memcpy(&b[88], &f.steps, 8); memcpy(&b[96], &f.seed, 8); memcpy(&b[104], &f.m, 8);
-    memcpy(&b[112], f.js.data(), 512);
-    for (uint64_t i = 0; i < T; i++) { memcpy(&b[TAMES_HEADER + TAMES_ENTRY * i], &f.x[i], 8); memcpy(&b[TAMES_HEADER + TAMES_ENTRY * i + 8], &f.d[i], 16); }
+    if (f.sym()) { memcpy(&b[112], &f.R, 4); memcpy(&b[120], &f.jumpscale, 8); }
+    memcpy(&b[head - 8 * (size_t)f.R], f.js.data(), 8 * (size_t)f.R);
+    for (uint64_t i = 0; i < T; i++) { memcpy(&b[head + TAMES_ENTRY * i], &f.x[i], 8); memcpy(&b[head + TAMES_ENTRY * i + 8], &f.d[i], 16); }
     const std::string tmp = path + ".temp";
     { std::ofstream o(tmp, std::ios::binary); o.write((const char *)b.data(), (std::streamsize)b.size()); if (!o) return false; }
     return rename(tmp.c_str(), path.c_str()) == 0;
 }
 
-// "" when the file is a complete tame table, else what is wrong with it; the file is only read
-std::string read_tames(const std::string &path, TamesFile &f)
+// "" when the file is a complete tame table of version `want`, else what is wrong with it; the file is only read.  Each reader refuses the other's
+// version with one line that says which walk the file belongs to.
+std::string read_tames(const std::string &path, TamesFile &f, uint32_t want = TAMES_VERSION)
 {
     std::ifstream in(path, std::ios::binary);
     if (!in) return "cannot open " + path;
@@ -46,20 +55,33 @@ std::string read_tames(const std::string &path, TamesFile &f)
     if (b.size() < 8 || memcmp(b.data(), TAMES_MAGIC, 8) != 0) return path + " is not a tame table (magic)";
     uint32_t version = 0;
     if (b.size() >= 12) memcpy(&version, &b[8], 4);
-    if (b.size() < 12 || version != TAMES_VERSION) return path + ": tame table version " + std::to_string(version) + ", this program reads version " + std::to_string(TAMES_VERSION);
+    if (b.size() < 12 || version != want)
+        return path + ": tame table version " + std::to_string(version) + ", this program reads version " + std::to_string(want) +
+               (version == TAMES_VERSION_SYM && want == TAMES_VERSION ? " (version 2 is a table of the symmetric walk: -ktamessym)" :
+                version == TAMES_VERSION && want == TAMES_VERSION_SYM ? " with -ktamessym (version 1 is a table of the plain walk: -ktames)" : "");
+    f.version = version;
+    const bool sym = f.sym();
+    const std::string wrong_length = path + ": wrong length for a tame table (" + std::to_string(b.size()) + " bytes)";
+    f.R = BSGS_KANGAROO_JUMPS; f.jumpscale = 1.0;
+    if (sym) {
+        if (b.size() < TAMES_FIXED_SYM) return wrong_length;
+        memcpy(&f.R, &b[112], 4); memcpy(&f.jumpscale, &b[120], 8);
+        if (f.R < 64 || f.R > BSGS_KANGAROO_SYM_MAX_JUMPS || (f.R & (f.R - 1))) return path + ": -kjumps " + std::to_string(f.R) + " (a power of two, 64..4096)";
+    }
+    const size_t head = (sym ? TAMES_FIXED_SYM : TAMES_FIXED) + 8 * (size_t)f.R;
     uint64_t T = 0;
-    if (b.size() >= TAMES_HEADER) memcpy(&T, &b[80], 8);
-    if (b.size() < TAMES_HEADER || !T || T > (1ull << 31) || b.size() != TAMES_HEADER + TAMES_ENTRY * T) return path + ": wrong length for a tame table (" + std::to_string(b.size()) + " bytes)";
+    if (b.size() >= head) memcpy(&T, &b[80], 8);
+    if (b.size() < head || !T || T > (1ull << 31) || b.size() != head + TAMES_ENTRY * T) return wrong_length;
     memcpy(&f.dp, &b[12], 4);
     if (f.dp > 32) return path + ": -dp " + std::to_string(f.dp);
     f.lo = hs::fe_from_le(&b[16]); f.hi = hs::fe_from_le(&b[48]);
     memcpy(&f.steps, &b[88], 8); memcpy(&f.seed, &b[96], 8); memcpy(&f.m, &b[104], 8);
-    f.js.resize(BSGS_KANGAROO_JUMPS);
-    memcpy(f.js.data(), &b[112], 512);
-    for (uint32_t j = 0; j < BSGS_KANGAROO_JUMPS; j++) if (!f.js[j]) return path + ": jump scalar " + std::to_string(j) + " is zero";
+    f.js.resize(f.R);
+    memcpy(f.js.data(), &b[head - 8 * (size_t)f.R], 8 * (size_t)f.R);
+    for (uint32_t j = 0; j < f.R; j++) if (!f.js[j]) return path + ": jump scalar " + std::to_string(j) + " is zero";
     f.x.resize(T); f.d.resize(T);
     for (uint64_t i = 0; i < T; i++) {
-        memcpy(&f.x[i], &b[TAMES_HEADER + TAMES_ENTRY * i], 8); memcpy(&f.d[i], &b[TAMES_HEADER + TAMES_ENTRY * i + 8], 16);
+        memcpy(&f.x[i], &b[head + TAMES_ENTRY * i], 8); memcpy(&f.d[i], &b[head + TAMES_ENTRY * i + 8], 16);
         if (i && f.x[i] <= f.x[i - 1]) return path + ": entries are not strictly ascending (entry " + std::to_string(i) + ")";
     }
     return "";
@@ -81,6 +103,28 @@ TamesPlan tames_plan(u128 W, uint64_t T, uint32_t dp)
     return t;
 }
 
+// the symmetric walk's defaults (tests/kangaroo_tames_sym_model.py plan): tame starts in [1, ceil(W/2) + E) with E = W / 16.  The walk on classes
+// diffuses: after n steps a kangaroo is about m sqrt(n) from its start with n points within that distance, so it meets its own trail with probability about
+// n^1.5 / m.  m is the largest that keeps the herd inside the covered region, m sqrt(n) = E / 2 with n = K / kn the steps of a generating kangaroo (kn: the
+// generating herd, all engines), never below the plain table's W / 2K; wild starts are spread over [-U, U), U = min(2^32, E / 4); the age limit is the plain table's
+uint64_t isqrt64(uint64_t v)
+{
+    uint64_t r = (uint64_t)std::sqrt((long double)v);
+    while (r * r > v) r--;
+    while ((r + 1) * (r + 1) <= v) r++;
+    return r;
+}
+TamesPlan tames_plan_sym(u128 W, uint64_t T, uint32_t dp, uint64_t kn)
+{
+    TamesPlan t = tames_plan(W, T, dp);
+    const uint64_t K = T << dp, n = std::max<uint64_t>(1, K / std::max<uint64_t>(kn, 1));
+    t.E = std::max<u128>(W / 16, 1);
+    t.m = std::max<uint64_t>(t.m, (uint64_t)std::min<u128>(((u128)1 << 62) - 1, t.E / (2 * isqrt64(n))));
+    t.U = std::max<u128>(1, std::min<u128>((u128)1 << 32, t.E / 4));
+    t.per_key = (double)(((long double)(W / 2) + (long double)t.E) / (long double)K);
+    return t;
+}
+
 std::string u128_hex(u128 v) { return hs::fe_to_hex(hs::sc_from_u128(v)); }
 
 // ---- the search rule without a device -------------------------------------------------------------------------------------------------------------------
@@ -89,9 +133,27 @@ public:
     enum What { FOUND, FALSE_MATCH, STALE, RESEED };
     struct Event { What what; uint32_t a; Scalar key; };
     TamesRule(const TamesFile &f, u128 W, const std::vector<Affine> &P, const std::vector<bool> &presolved, uint64_t n_wild, uint64_t age_launches)
-        : f_(f), W_(W), P_(P), known_(presolved), key_(P.size()), asg_((uint32_t)P.size(), presolved, n_wild), age_(n_wild, 0), limit_(age_launches)
+        : f_(f), W_(W), base_(f.sym() ? hs::sc_add(f.lo, hs::sc_from_u128(W / 2)) : f.lo), P_(P), known_(presolved), key_(P.size()),
+          asg_((uint32_t)P.size(), presolved, n_wild), age_(n_wild, 0), limit_(age_launches)
     {
-        for (size_t k = 0; k < P.size(); k++) { if (presolved[k]) { key_[k] = f.lo; solved_++; } same_[hs::compress_pubkey(P[k])].push_back((uint32_t)k); }
+        for (size_t k = 0; k < P.size(); k++) { if (presolved[k]) { key_[k] = base_; solved_++; } same_[hs::compress_pubkey(P[k])].push_back((uint32_t)k); }
+    }
+    // what offsets are counted from: a, or with a table of the symmetric walk a + floor(W/2); a key equal to base*G is solved up front
+    const Scalar &base() const { return base_; }
+    uint64_t cycles() const { return cycles_; }
+    // key k is base + off when off lies in the range as counted from base and that multiple of G is P_k: every equal point of the list is solved with it
+    bool accept(uint32_t k, i128 off, std::vector<Event> &ev)
+    {
+        const i128 lowest = f_.sym() ? -(i128)(W_ / 2) : 0;
+        if (off < lowest || off >= lowest + (i128)W_) return false;
+        const Scalar cand = hs::sc_add(base_, sc_from_i128(off));
+        const Affine q = hs::point_mul(hs::G, cand);
+        if (q.inf || !hs::fe_equal(q.x, P_[k].x) || !hs::fe_equal(q.y, P_[k].y)) return false;
+        for (uint32_t o : same_[hs::compress_pubkey(P_[k])]) if (!known_[o]) {
+            known_[o] = true; key_[o] = cand; solved_++; asg_.solved(o);
+            ev.push_back(Event{FOUND, o, cand});
+        }
+        return true;
     }
     bool known(uint32_t k) const { return known_[k]; }
     const Scalar &key(uint32_t k) const { return key_[k]; }
@@ -104,27 +166,21 @@ public:
     // one record the device handed back: flags and offset of the kangaroo, reserved = entry number + 1 or 0
     void record(uint32_t flags, uint32_t reserved, i128 d, std::vector<Event> &ev)
     {
-        if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; ev.push_back(Event{RESEED, 0, Scalar()}); return; }
+        if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; if (flags & BSGS_KANGAROO_CYCLE) cycles_++; ev.push_back(Event{RESEED, 0, Scalar()}); return; }
         if (!reserved || reserved > f_.x.size()) return;               // (the device hands back nothing else)
         matches_++;
         const uint32_t k = (flags >> BSGS_KANGAROO_KEY_SHIFT) & 0xFFFFu;
         if (k >= P_.size() || known_[k]) { ev.push_back(Event{STALE, k, Scalar()}); return; }
-        const i128 off = f_.d[reserved - 1] - d;                       // k' = d_T - d_W
-        Scalar cand;
-        if (off >= 0 && (u128)off < W_) {
-            cand = hs::sc_add(f_.lo, hs::sc_from_u128((u128)off));
-            const Affine q = hs::point_mul(hs::G, cand);
-            if (!q.inf && hs::fe_equal(q.x, P_[k].x) && hs::fe_equal(q.y, P_[k].y)) {
-                for (uint32_t o : same_[hs::compress_pubkey(P_[k])]) if (!known_[o]) {       // equal points of the list are solved with it
-                    known_[o] = true; key_[o] = cand; solved_++; asg_.solved(o);
-                    ev.push_back(Event{FOUND, o, cand});
-                }
-                return;
-            }
-        }
+        const i128 dT = f_.d[reserved - 1];
+        if (f_.sym()) {                                                // sigma Q_k + d_W G = eps d_T G: k'' = sigma (eps d_T - d_W), eps = +1 first
+            const i128 sg = flags & BSGS_KANGAROO_NEG ? -1 : 1;
+            if (accept(k, sg * (dT - d), ev) || accept(k, sg * (-dT - d), ev)) return;
+        } else if (accept(k, dT - d, ev)) return;                      // k' = d_T - d_W
         false_++;
         ev.push_back(Event{FALSE_MATCH, k, Scalar()});
     }
+    // a wild kangaroo of key k seeded with the offset u stands at infinity: Q_k = -u G, the candidate is -u (the symmetric walk's range holds such keys)
+    void start_at_infinity(uint32_t k, i128 u, std::vector<Event> &ev) { if (k < P_.size() && !known_[k]) accept(k, -u, ev); }
     // a launch of wild kangaroos [first, first + n) ended: those that have walked more than the limit since their start are named
     void launch_done(uint64_t first, uint64_t n, std::vector<uint64_t> &aged)
     {
@@ -135,6 +191,7 @@ public:
 private:
     const TamesFile &f_;
     const u128 W_;
+    const Scalar base_;
     const std::vector<Affine> &P_;
     std::vector<bool> known_;
     std::vector<Scalar> key_;
@@ -142,7 +199,7 @@ private:
     std::vector<uint32_t> age_;
     const uint64_t limit_;
     std::map<std::string, std::vector<uint32_t>> same_;
-    uint64_t matches_ = 0, false_ = 0, reseeds_ = 0;
+    uint64_t matches_ = 0, false_ = 0, reseeds_ = 0, cycles_ = 0;
     uint32_t solved_ = 0;
 };
 
@@ -159,21 +216,35 @@ struct GenMode : Mode {
         saves = false;
         // dp: the command line's, else about (log2(W / T)) / 2 - 4: the trails stay a small part of the range while a wild walk to the next DP stays short
         dp_fixed = c.dp >= 0 ? c.dp : (int)std::max(0.0, std::min(14.0, std::floor(std::log2((double)p.W / (double)T) / 2.0) - 4.0));
-        plan = tames_plan(p.W, T, (uint32_t)dp_fixed);
+        plan = tames_plan(p.W, T, (uint32_t)dp_fixed);                 // (-kwalk sym: planned() replaces it once the herd is known)
         mean_jump = (double)plan.m;
         expected = 2.0 * (double)T * std::ldexp(1.0, dp_fixed);
         herd_label = "herd (GPU, all tame), engine ";
         span = p.W + plan.E - 1;
+        if (c.tames_sym) {                                             // -kwalk sym: R jump points, a launch longer than the cycle window
+            jumps = c.jumps ? c.jumps : 1024u;
+            jumpscale = c.jumpscale != 0.0 ? c.jumpscale : 1.0;
+            min_launch = 2.0 * BSGS_KANGAROO_CYCLE_WINDOW;
+        }
         map.reserve((size_t)T * 2);
+    }
+    // -kwalk sym: the mean jump depends on the steps a kangaroo of this herd walks; mean -kjumpscale * m, starts in [1, ceil(W/2) + E)
+    void planned(const Prologue &p) override
+    {
+        if (!c.tames_sym) return;
+        plan = tames_plan_sym(p.W, T, p.pl.dp, p.pl.kn * p.pl.engines);
+        mean_jump = std::max(1.0, std::min(std::ldexp(1.0, 62), jumpscale * (double)plan.m));
+        span = (p.W + 1) / 2 + plan.E - 1;
     }
     std::string fingerprint(const Prologue &, const WorkHeader &) const override { return ""; }
     bool before_devices(Prologue &p) override { pro = &p; p.t0 = Clock::now(); return true; }
     const char *setup(bsgs_dev *dev) override
     {
         const Plan &pl = pro->pl;
+        if (c.tames_sym) return bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) == BSGS_OK ? nullptr : "bsgs_kangaroo_setup_sym";
         return bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) == BSGS_OK ? nullptr : "bsgs_kangaroo_setup";
     }
-    // every kangaroo is tame: t uniform in [1, W + E), d = t
+    // every kangaroo is tame: t uniform in [1, W + E), with -kwalk sym in [1, ceil(W/2) + E), d = t
     const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) override
     {
         const size_t n = idx.empty() ? (size_t)pro->pl.kn : idx.size();
@@ -221,7 +292,9 @@ int tames_generate(const KangConfig &c)
            (unsigned long long)c.ktn);
     GenMode mode(c, p);
     p.complete(c, mode);
-    printf("Plan: mean jump m = %llu, tame starts reach E = 0x%s past the range, -dp %u\n", (unsigned long long)mode.plan.m, u128_hex(mode.plan.E).c_str(), p.pl.dp);
+    if (c.tames_sym) printf("Plan: symmetric walk, %u jump points, jump scale %g, mean jump m = %llu, tame starts reach E = 0x%s past the half range, -dp %u\n", mode.jumps, mode.jumpscale,
+                            (unsigned long long)mode.mean_jump, u128_hex(mode.plan.E).c_str(), p.pl.dp);
+    else printf("Plan: mean jump m = %llu, tame starts reach E = 0x%s past the range, -dp %u\n", (unsigned long long)mode.plan.m, u128_hex(mode.plan.E).c_str(), p.pl.dp);
     Shared sh(p);
     const Outcome o = run(c, p, sh, mode);
     const double secs = since(p.t0);
@@ -232,6 +305,7 @@ int tames_generate(const KangConfig &c)
     }
     TamesFile f;
     f.dp = p.pl.dp; f.lo = p.lo; f.hi = p.hi; f.steps = sh.steps.load(); f.seed = p.wh.seed; f.m = mode.plan.m; f.js = p.js;
+    if (c.tames_sym) { f.version = TAMES_VERSION_SYM; f.R = mode.jumps; f.jumpscale = mode.jumpscale; f.m = (uint64_t)mode.mean_jump; }
     std::vector<std::pair<uint64_t, i128>> en(mode.map.begin(), mode.map.end());
     std::sort(en.begin(), en.end());
     en.resize((size_t)c.ktn);
@@ -253,7 +327,8 @@ struct SearchMode : Mode {
         dp_fixed = (int)f.dp;
         mean_jump = (double)f.m;
         jump_scalars = f.js.data();                                    // the search walks with exactly the generator's jumps
-        plan = tames_plan(p.W, f.x.size(), f.dp);
+        plan = f.sym() ? tames_plan_sym(p.W, f.x.size(), f.dp, 1) : tames_plan(p.W, f.x.size(), f.dp);      // (E, U, A: they do not depend on the herd; m is the file's)
+        if (f.sym()) { jumps = f.R; jumpscale = f.jumpscale; min_launch = 2.0 * BSGS_KANGAROO_CYCLE_WINDOW; }      // a launch longer than the cycle window
         herd_label = "herd (GPU, all wild), engine ";
     }
     std::string fingerprint(const Prologue &, const WorkHeader &) const override { return ""; }
@@ -272,12 +347,13 @@ struct SearchMode : Mode {
         pro = &p;
         { Config rc; rc.dir = c.dir; read_recovery(rc); }             // (win.txt starts empty, as on the BSGS path)
         p.t0 = Clock::now();
-        const Affine naG = hs::affine_neg(hs::point_mul(hs::G, p.lo));
+        base = f.sym() ? hs::sc_add(p.lo, hs::sc_from_u128(p.W / 2)) : p.lo;      // -kwalk sym: offsets are counted from the middle of the range
+        const Affine naG = hs::affine_neg(hs::point_mul(hs::G, base));
         presolved.assign(L, false);
         qxy.resize(64 * (size_t)L);
         for (uint32_t k = 0; k < L; k++) {                             // Q_k = P_k - a*G; a key equal to a*G is solved here and keeps its slot
             Affine Q = hs::point_add(P[k], naG);
-            if (Q.inf) { presolved[k] = true; report(k, p.lo); Q = hs::G; }
+            if (Q.inf) { presolved[k] = true; report(k, base); Q = hs::G; }
             hs::affine_to_le(Q, &qxy[64 * (size_t)k], &qxy[64 * (size_t)k + 32]);
         }
         open0 = L - (uint32_t)found_n;
@@ -296,17 +372,25 @@ struct SearchMode : Mode {
         printf("Tame table: %zu entries at -dp %u, mean jump %llu; about 2^%.2f steps per key; a wild kangaroo starts afresh after %llu launches\n", f.x.size(), f.dp,
                (unsigned long long)f.m, std::log2(plan.per_key + std::ldexp(1.0, (int)f.dp)), (unsigned long long)launches);
         off0.resize(pl.engines);
-        for (uint32_t e = 0; e < pl.engines; e++) { off0[e].resize(pl.kn); for (uint64_t i = 0; i < pl.kn; i++) off0[e][i] = (i128)(draw128(s.rng) % plan.U); }
+        for (uint32_t e = 0; e < pl.engines; e++) { off0[e].resize(pl.kn); for (uint64_t i = 0; i < pl.kn; i++) off0[e][i] = wild_offset(s.rng); }
+        if (f.sym()) entries.assign(pl.engines, std::vector<uint32_t>(pl.cap));
         last_solved = rule->solved();
     }
+    // u uniform in [0, U); with a table of the symmetric walk in [-U, U)
+    i128 wild_offset(uint64_t &rng) const { return f.sym() ? (i128)(draw128(rng) % (2 * plan.U)) - (i128)plan.U : (i128)(draw128(rng) % plan.U); }
     const char *setup(bsgs_dev *dev) override
     {
         const Plan &pl = pro->pl;
+        if (f.sym()) {                                                 // the symmetric herd whose records name their key beside the flags
+            if (bsgs_kangaroo_setup_sym_keys(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup_sym_keys";
+            if (bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) return "bsgs_kangaroo_set_keys";
+            return bsgs_kangaroo_tames_install_keys(dev, f.x.data(), f.x.size()) == BSGS_OK ? nullptr : "bsgs_kangaroo_tames_install_keys";
+        }
         if (bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup";
         if (bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) return "bsgs_kangaroo_set_keys";
         return bsgs_kangaroo_tames_install(dev, f.x.data(), f.x.size()) == BSGS_OK ? nullptr : "bsgs_kangaroo_tames_install";
     }
-    // every kangaroo is wild: kangaroo of key k at Q_k + u*G, u uniform in [0, U), flags WILD | k << 8
+    // every kangaroo is wild: kangaroo of key k at Q_k + u*G, u uniform in [0, U), flags WILD | k << 8 (the symmetric herd: the key beside the flags)
     const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &s) override
     {
         const uint64_t kn = pro->pl.kn, w0 = (uint64_t)e * kn;
@@ -323,21 +407,51 @@ struct SearchMode : Mode {
                 uint32_t k = 0;
                 if (!rule->reseed(w0 + i, &k)) continue;               // no key is open: the kangaroo rests
                 use.push_back(i); fl.push_back(BSGS_KANGAROO_WILD); key.push_back(k);
-                d.push_back((i128)(draw128(s.rng) % plan.U));
+                d.push_back(wild_offset(s.rng));
             }
             if (use.empty()) return nullptr;
         }
         uint32_t ninf = 0, first = 0;
         if (bsgs_kangaroo_seed_keys(dev, use.empty() ? nullptr : use.data(), 0, (uint32_t)d.size(), (const uint8_t *)d.data(), fl.data(), key.data(), &ninf, &first) != BSGS_OK)
             return "bsgs_kangaroo_seed_keys";
-        if (ninf) s.push_reseed(e, use.empty() ? first : use[first]);  // Q_k + u*G at infinity names a key below the range: the kangaroo starts again
+        if (ninf) {
+            // Q_k + u*G at infinity names the key base - u: below the plain walk's range, but maybe in the symmetric walk's.  Either way the kangaroo starts again
+            if (f.sym()) {
+                std::lock_guard<std::mutex> lt(s.tab_m);
+                std::vector<TamesRule::Event> ev;
+                rule->start_at_infinity(key[first], d[first], ev);
+                found_events(ev, s);
+            }
+            s.push_reseed(e, use.empty() ? first : use[first]);
+        }
         return nullptr;
+    }
+    // under s.tab_m: the keys an event list names as found go to win.txt, and their kangaroos start afresh
+    void found_events(const std::vector<TamesRule::Event> &ev, Shared &s)
+    {
+        const uint64_t kn = pro->pl.kn;
+        for (const TamesRule::Event &x : ev) {
+            if (x.what != TamesRule::FOUND) continue;
+            report(x.a, x.key);
+            for (uint64_t w = 0; w < rule->keys().size(); w++) if (rule->keys()[w] == x.a) s.push_reseed((uint32_t)(w / kn), (uint32_t)(w % kn));
+        }
+        if (rule->solved() == L) s.stop = true;
     }
     // the launch, the match on the device, the matched and DEAD records alone; then the kangaroos that have walked too long
     int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &s) override
     {
         uint64_t n_seen = 0;
-        const int rc = bsgs_kangaroo_run_tames(dev, steps, recs, cap, n, &n_seen, dropped, nullptr);
+        int rc;
+        if (f.sym()) {
+            // the records as the walk wrote them, the entry numbers beside them: brought into the form of the plain herd's -- the key into the flags'
+            // key bits (where the walk keeps its last jump index, which means nothing here), entry number + 1 into `reserved`
+            rc = bsgs_kangaroo_run_tames_keys(dev, steps, recs, entries[e].data(), std::min<uint32_t>(cap, (uint32_t)entries[e].size()), n, &n_seen, dropped, nullptr);
+            if (rc == BSGS_OK) for (uint32_t i = 0; i < *n; i++) {
+                const uint32_t type = recs[i].flags & (BSGS_KANGAROO_WILD | BSGS_KANGAROO_NEG | BSGS_KANGAROO_CYCLE | BSGS_KANGAROO_DEAD);
+                recs[i].flags = type | (recs[i].reserved & 0xFFFFu) << BSGS_KANGAROO_KEY_SHIFT;
+                recs[i].reserved = entries[e][i];
+            }
+        } else rc = bsgs_kangaroo_run_tames(dev, steps, recs, cap, n, &n_seen, dropped, nullptr);
         if (rc != BSGS_OK) return rc;
         seen += n_seen;
         std::vector<uint64_t> aged;
@@ -352,14 +466,8 @@ struct SearchMode : Mode {
         i128 d;
         memcpy(&d, r.d, 16);
         rule->record(r.flags, r.reserved, d, ev);
-        const uint64_t kn = pro->pl.kn;
-        for (const TamesRule::Event &x : ev) {
-            if (x.what == TamesRule::RESEED) s.push_reseed(e, r.kangaroo);
-            if (x.what != TamesRule::FOUND) continue;
-            report(x.a, x.key);
-            for (uint64_t w = 0; w < rule->keys().size(); w++) if (rule->keys()[w] == x.a) s.push_reseed((uint32_t)(w / kn), (uint32_t)(w % kn));
-        }
-        if (rule->solved() == L) s.stop = true;
+        for (const TamesRule::Event &x : ev) if (x.what == TamesRule::RESEED) s.push_reseed(e, r.kangaroo);
+        found_events(ev, s);
         return true;
     }
     uint32_t entry_flags(uint32_t) const override { return 0u; }
@@ -387,6 +495,8 @@ struct SearchMode : Mode {
     std::vector<bool> presolved;
     std::vector<uint8_t> qxy;
     std::vector<std::vector<i128>> off0;
+    Scalar base;                                                       // what offsets are counted from: a, or a + floor(W/2) with a table of the symmetric walk
+    std::vector<std::vector<uint32_t>> entries;                        // per engine, the symmetric herd: entry number + 1 of each record of a launch
     std::atomic<uint64_t> seen{0};
     int found_n = 0;
     uint32_t open0 = 0, last_solved = 0;
@@ -423,8 +533,8 @@ int tames_search(const KangConfig &c)
     TamesFile f;
     std::string path = c.ktames;
     { struct stat sb; if (stat(path.c_str(), &sb) != 0 && stat((c.dir + "/" + path).c_str(), &sb) == 0) path = c.dir + "/" + path; }
-    const std::string bad = read_tames(path, f);
-    if (!bad.empty()) die("-ktames: " + bad);
+    const std::string bad = read_tames(path, f, c.tames_sym ? TAMES_VERSION_SYM : TAMES_VERSION);
+    if (!bad.empty()) die(std::string(c.tames_sym ? "-ktamessym: " : "-ktames: ") + bad);
     std::vector<std::string> pub_hex;
     if (!c.infile.empty()) { Config fc; fc.infile = c.infile; pub_hex = read_pubs(fc); if (pub_hex.empty()) die("No public keys in " + c.infile); }
     else pub_hex.push_back(c.pub);
@@ -438,6 +548,7 @@ int tames_search(const KangConfig &c)
     SearchMode mode(c, P, f, p);
     p.complete(c, mode);
     if (!p.go) return 0;
+    if (f.sym()) printf("Kangaroo: symmetric walk (negation map), %u jump points, jump scale %g, from the table\n", f.R, f.jumpscale);
     if (c.verify) tames_verify(f, p.gpus[0]);
     Shared sh(p);
     mode.prepare(p, sh);
@@ -447,6 +558,7 @@ int tames_search(const KangConfig &c)
     else if (o != DONE) printf("\nKangaroo: stopped after %llu steps (%s), %u of %u keys open\n", (unsigned long long)sh.steps.load(), o == BUDGET ? "-ksteps" : "signal", L - r.solved(), L);
     printf("Job time %.2fs, %.3e kangaroo steps, %llu records seen (%llu dropped), %llu matches, %llu false matches, %llu re-seeds\n", since(p.t0), (double)sh.steps.load(),
            (unsigned long long)mode.seen.load(), (unsigned long long)sh.dropped.load(), (unsigned long long)r.matches(), (unsigned long long)r.false_matches(), (unsigned long long)r.reseeds());
+    if (f.sym()) printf("Symmetric walk: %llu cycles retired\n", (unsigned long long)r.cycles());
     for (uint32_t e = 0; e < p.pl.engines; e++) printf("Engine %u (GPU #%d): %llu records\n", e, p.gpus[e], (unsigned long long)sh.engine_records[e]);
     printf("Found %d of %u\n", mode.found_n, L);
     fflush(stdout);
@@ -456,15 +568,19 @@ int tames_search(const KangConfig &c)
 
 int kangaroo_tames_main(const KangConfig &c) { return c.ktamesgen.empty() ? tames_search(c) : tames_generate(c); }
 
-// -selftest kangaroo-tames FILE [pk pke]: the header fields of a tame table, its ordering, and with a range whether it is the table's
-int kangaroo_tames_selftest(const std::vector<std::string> &a)
+// -selftest kangaroo-tames [sym] FILE [pk pke]: the header fields of a tame table, its ordering, and with a range whether it is the table's.  sym: the reader
+// of -ktamessym (version 2; two more lines, "jumps <R>" and "jump scale <s>"), else the reader of -ktames (version 1)
+int kangaroo_tames_selftest(const std::vector<std::string> &args)
 {
+    const bool sym = !args.empty() && args[0] == "sym";
+    const std::vector<std::string> a(args.begin() + (sym ? 1 : 0), args.end());
     if (a.size() != 1 && a.size() != 3) return 2;
     TamesFile f;
-    const std::string bad = read_tames(a[0], f);
+    const std::string bad = read_tames(a[0], f, sym ? TAMES_VERSION_SYM : TAMES_VERSION);
     if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
-    printf("version %u\ndp %u\npk %s\npke %s\nentries %zu\nsteps %llu\nseed 0x%llx\nmean jump %llu\n", TAMES_VERSION, f.dp, hs::fe_to_hex(f.lo).c_str(), hs::fe_to_hex(f.hi).c_str(), f.x.size(),
+    printf("version %u\ndp %u\npk %s\npke %s\nentries %zu\nsteps %llu\nseed 0x%llx\nmean jump %llu\n", f.version, f.dp, hs::fe_to_hex(f.lo).c_str(), hs::fe_to_hex(f.hi).c_str(), f.x.size(),
            (unsigned long long)f.steps, (unsigned long long)f.seed, (unsigned long long)f.m);
+    if (sym) printf("jumps %u\njump scale %g\n", f.R, f.jumpscale);
     if (a.size() == 3) {
         Scalar lo, hi;
         if (!hs::fe_from_hex(lo, cut_hex(a[1])) || !hs::fe_from_hex(hi, cut_hex(a[2]))) return 2;
@@ -494,24 +610,29 @@ int kangaroo_tames_image_selftest(const std::vector<std::string> &)
 //   L                                                        a launch of every kangaroo has ended
 // One line per event: "miss", "found <k> <key hex>", "false", "stale", "reseed <kangaroo> <key>", "aged <kangaroo> <key>", and after a found key, for each of
 // its kangaroos in ascending order, "reassign <kangaroo> <key>" ("rest <kangaroo>" when no key is open); then "summary <matches> <false matches> <re-seeds> <solved>".
-int kangaroo_tames_search_selftest(const std::vector<std::string> &a)
+// -selftest kangaroo-tames-search sym FILE ...: the rule of a table of the symmetric walk (version 2).  Record types W and N (a wild kangaroo, N: with NEG) in
+// the place of R, D and C,<kangaroo> (C: the cycle check's DEAD | CYCLE record); a key equal to (pk + W/2)*G is presolved; the summary line ends with the
+// cycles retired.
+int kangaroo_tames_search_selftest(const std::vector<std::string> &args)
 {
+    const bool sym = !args.empty() && args[0] == "sym";
+    const std::vector<std::string> a(args.begin() + (sym ? 1 : 0), args.end());
     if (a.size() < 4) return 2;
     TamesFile f;
-    const std::string bad = read_tames(a[0], f);
+    const std::string bad = read_tames(a[0], f, sym ? TAMES_VERSION_SYM : TAMES_VERSION);
     if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
     std::vector<Affine> P;
     if (!parse_pubs(a[1], P) || P.empty() || P.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
     const uint64_t n_wild = strtoull(a[2].c_str(), nullptr, 10), limit = strtoull(a[3].c_str(), nullptr, 10);
     if (!n_wild || n_wild > (1u << 20)) return 2;
-    const Affine aG = hs::point_mul(hs::G, f.lo);
+    const Affine aG = hs::point_mul(hs::G, sym ? hs::sc_add(f.lo, hs::sc_from_u128(range_width(f.lo, f.hi) / 2)) : f.lo);
     std::vector<bool> presolved(P.size(), false);
     bool open = false;
     for (size_t k = 0; k < P.size(); k++) {
         presolved[k] = hs::fe_equal(P[k].x, aG.x) && hs::fe_equal(P[k].y, aG.y);
         if (presolved[k]) printf("presolved %zu\n", k); else open = true;
     }
-    if (!open) { printf("summary 0 0 0 %zu\n", P.size()); return 0; }
+    if (!open) { printf(sym ? "summary 0 0 0 %zu 0\n" : "summary 0 0 0 %zu\n", P.size()); return 0; }
     TamesRule rule(f, range_width(f.lo, f.hi), P, presolved, n_wild, limit);
     auto start_afresh = [&](const char *word, uint64_t w) {
         uint32_t k = 0;
@@ -526,18 +647,18 @@ int kangaroo_tames_search_selftest(const std::vector<std::string> &a)
             rule.launch_done(0, n_wild, aged);
             for (uint64_t v : aged) start_afresh("aged", v);
             continue;
-        } else if (t.size() == 2 && t[0] == "D") {
+        } else if (t.size() == 2 && (t[0] == "D" || (sym && t[0] == "C"))) {
             w = strtoull(t[1].c_str(), nullptr, 10);
             if (w >= n_wild) return 2;
-            rule.record(BSGS_KANGAROO_WILD | BSGS_KANGAROO_DEAD | rule.key_of(w) << BSGS_KANGAROO_KEY_SHIFT, 0, 0, ev);
-        } else if (t.size() == 4 && t[0] == "R") {
+            rule.record(BSGS_KANGAROO_WILD | BSGS_KANGAROO_DEAD | (t[0] == "C" ? BSGS_KANGAROO_CYCLE : 0u) | rule.key_of(w) << BSGS_KANGAROO_KEY_SHIFT, 0, 0, ev);
+        } else if (t.size() == 4 && (sym ? t[0] == "W" || t[0] == "N" : t[0] == "R")) {
             Scalar x, dd;
             if (!hs::fe_from_hex(x, t[1]) || !hs::fe_from_hex(dd, t[2]) || dd.l[2] || dd.l[3]) return 2;
             w = strtoull(t[3].c_str(), nullptr, 10);
             if (w >= n_wild) return 2;
             const auto it = std::lower_bound(f.x.begin(), f.x.end(), x.l[0]);
             if (it == f.x.end() || *it != x.l[0]) { printf("miss\n"); continue; }
-            rule.record(BSGS_KANGAROO_WILD | rule.key_of(w) << BSGS_KANGAROO_KEY_SHIFT, (uint32_t)(it - f.x.begin()) + 1u, (i128)(((u128)dd.l[1] << 64) | dd.l[0]), ev);
+            rule.record(BSGS_KANGAROO_WILD | (t[0] == "N" ? BSGS_KANGAROO_NEG : 0u) | rule.key_of(w) << BSGS_KANGAROO_KEY_SHIFT, (uint32_t)(it - f.x.begin()) + 1u, (i128)(((u128)dd.l[1] << 64) | dd.l[0]), ev);
         } else return 2;
         for (const TamesRule::Event &e : ev) switch (e.what) {
             case TamesRule::FALSE_MATCH: printf("false\n"); break;
@@ -551,6 +672,8 @@ int kangaroo_tames_search_selftest(const std::vector<std::string> &a)
             }
         }
     }
-    printf("summary %llu %llu %llu %u\n", (unsigned long long)rule.matches(), (unsigned long long)rule.false_matches(), (unsigned long long)rule.reseeds(), rule.solved());
+    printf("summary %llu %llu %llu %u", (unsigned long long)rule.matches(), (unsigned long long)rule.false_matches(), (unsigned long long)rule.reseeds(), rule.solved());
+    if (sym) printf(" %llu", (unsigned long long)rule.cycles());
+    printf("\n");
     return 0;
 }

@@ -29,7 +29,7 @@ NATIVE_SYMBOLS = [
     "bsgs_table_census", "bsgs_table_lookup", "bsgs_broadcast_tables_ex", "bsgs_startup_ext_tables", "bsgs_build_baby_table_ext_slice", "bsgs_build_overflow_set", "bsgs_debug_fabric_selftest", "bsgs_share_tables",
     "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym", "bsgs_kangaroo_setup_sym_keys",
     "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_kangaroo_verify", "bsgs_kangaroo_verify_points", "bsgs_selftest_fe3",
-    "bsgs_kangaroo_tames_image", "bsgs_kangaroo_tames_install", "bsgs_kangaroo_run_tames",
+    "bsgs_kangaroo_tames_image", "bsgs_kangaroo_tames_install", "bsgs_kangaroo_run_tames", "bsgs_kangaroo_tames_install_keys", "bsgs_kangaroo_run_tames_keys",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
@@ -194,6 +194,9 @@ def lib():
             "bsgs_kangaroo_tames_image": [C.POINTER(C.c_uint64), C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)],
             "bsgs_kangaroo_tames_install": [vp, C.POINTER(C.c_uint64), C.c_uint64],
             "bsgs_kangaroo_run_tames": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
+            "bsgs_kangaroo_tames_install_keys": [vp, C.POINTER(C.c_uint64), C.c_uint64],
+            "bsgs_kangaroo_run_tames_keys": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_float)],
         }
         for name, args in sig.items():
             fn = getattr(L, name, None)
@@ -742,6 +745,21 @@ class Device:
         _chk(self.L.bsgs_kangaroo_run_tames(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(dropped), C.byref(ms)))
         out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
                 "entry": r.reserved - 1 if r.reserved else None} for r in recs[:n.value]]
+        return out, seen.value, dropped.value, ms.value
+
+    def kangaroo_tames_install_keys(self, tags):
+        """kangaroo_tames_install for the herd of kangaroo_setup_sym_keys, whose records keep their key"""
+        _chk(self.L.bsgs_kangaroo_tames_install_keys(self.h, (C.c_uint64 * max(1, len(tags)))(*tags), len(tags)))
+
+    def kangaroo_run_tames_keys(self, steps, max_recs=None):
+        """kangaroo_run_tames for the herd of kangaroo_setup_sym_keys: every record also has "key" (the word the walk wrote), and "entry" comes from the
+        parallel array (entry number, None for a DEAD record that matched nothing); max_recs: a host buffer smaller than the record capacity"""
+        cap = max(1, self._kang_cap if max_recs is None else max_recs)
+        recs, ent = (KangarooRecord * cap)(), (C.c_uint32 * cap)()
+        n, seen, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _chk(self.L.bsgs_kangaroo_run_tames_keys(self.h, steps, recs, ent, cap, C.byref(n), C.byref(seen), C.byref(dropped), C.byref(ms)))
+        out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
+                "key": r.reserved, "entry": e - 1 if e else None} for r, e in zip(recs[:n.value], ent[:n.value])]
         return out, seen.value, dropped.value, ms.value
 
     def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):

@@ -9,6 +9,7 @@ the herd of bsgs_kangaroo_setup_sym_keys, whose kernel entry point reads a kanga
 
 --tames N installs a tame table of N entries (bsgs_kangaroo_tames_install; tags that no record meets, so every lookup ends in a miss, as all but a handful
 do in a search) and times bsgs_kangaroo_run_tames and bsgs_kangaroo_run in turn, launch by launch: the difference of their kernel times is the match.
+With --sym --keys the table is that of the keyed herd (bsgs_kangaroo_tames_install_keys, bsgs_kangaroo_run_tames_keys: the search of -ktamessym).
 
 The starts are 65536 distinct points P0 + i*G, repeated over the herd (the walk's cost does not depend on which point a kangaroo stands on; repeats only
 make their DPs coincide)."""
@@ -60,8 +61,6 @@ def main():
     a = ap.parse_args()
     if a.keys and not a.sym:
         ap.error("--keys goes with --sym")
-    if a.tames and a.keys:
-        ap.error("--tames: the plain herd, or --sym without --keys")
     dev = pybsgs.Device(0)
     L = dev.L
     cus = C.c_int()
@@ -95,12 +94,16 @@ def main():
         import numpy as np
         t0 = time.perf_counter()
         tags = np.arange(1, a.tames + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)      # an odd multiplier: pairwise different
-        pybsgs._chk(L.bsgs_kangaroo_tames_install(dev.h, tags.ctypes.data_as(C.POINTER(C.c_uint64)), a.tames))
+        pybsgs._chk((L.bsgs_kangaroo_tames_install_keys if a.keys else L.bsgs_kangaroo_tames_install)(dev.h, tags.ctypes.data_as(C.POINTER(C.c_uint64)), a.tames))
         install_s = time.perf_counter() - t0
         seen = C.c_uint64()
+        entries = (C.c_uint32 * (1 << 22))()
 
         def launch_tames():
-            pybsgs._chk(L.bsgs_kangaroo_run_tames(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(dropped), C.byref(ms)))
+            if a.keys:
+                pybsgs._chk(L.bsgs_kangaroo_run_tames_keys(dev.h, a.steps, recs, entries, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(dropped), C.byref(ms)))
+            else:
+                pybsgs._chk(L.bsgs_kangaroo_run_tames(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(dropped), C.byref(ms)))
             return ms.value, seen.value, cnt.value
 
         for _ in range(a.warmup):
@@ -114,7 +117,7 @@ def main():
             nrec += r
             back += m
         match = (sum(both) - sum(plain)) / len(both)
-        res = {"what": "kangaroo walk with a tame table matched on the device, one engine, full herd" + (", symmetric walk" if a.sym else ""), "gpu": dev.name(), "kangaroos": n,
+        res = {"what": "kangaroo walk with a tame table matched on the device, one engine, full herd" + (", symmetric walk" if a.sym else "") + (", a key per kangaroo" if a.keys else ""), "gpu": dev.name(), "kangaroos": n,
                "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp, "launches": a.launches, "tame_entries": a.tames, "image_bytes": 64 * max(64, 1 << (max(a.tames - 1, 1) // 2).bit_length()),
                "install_s": install_s, "ms_per_launch_walk": sum(plain) / len(plain), "ms_per_launch_walk_and_match": sum(both) / len(both), "ms_match": match,
                "match_share": match / (sum(both) / len(both)), "records_per_launch": nrec / a.launches, "records_returned_per_launch": back / a.launches,
