@@ -14,7 +14,9 @@ int bsgs_fail(int code, const char *fmt, ...);
     } while (0)
 #define fail bsgs_fail
 
-// kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip, kangaroo_seed_keys.hip: the comb table, the staging of a seed call and the key list;
+#define KANG_REC_HEADER 64u                                 // a record buffer (the walk's rec, the match's tames_rec): u64 count of records, then records from byte 64
+
+// kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table, the staging of a seed call and the key list;
 // kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;

@@ -11,7 +11,6 @@
 #define KANG_TABLE_OFF (4u * KANG_REGION)                   // the jump table behind the inversion regions: x[64] | y[64] | s[64] (4608 bytes)
 #define KANG_TABLE_BYTES (KANG_NJ * 32u * 2u + KANG_NJ * 8u)
 #define KANG_LDS (KANG_TABLE_OFF + KANG_TABLE_BYTES)
-#define KANG_REC_HEADER 64u                                 // record buffer: u64 count of records the launch produced, then records from byte 64
 
 struct KangArgs {
     u32x4 *st;             // [5][N]: x.lo, x.hi, y.lo, y.hi, d (128-bit, two's complement)
@@ -379,10 +378,13 @@ void bsgs_kangaroo_release(bsgs_dev *d)
 static_assert(sizeof(bsgs_kangaroo_state) == 96, "state record: 96 bytes");
 static_assert(sizeof(bsgs_kangaroo_record) == 64, "DP record: 64 bytes");
 
-// the herd of both walks; n_jumps = 0: the plain walk's 64 points in its LDS layout x[64] | y[64] | s[64]; else the symmetric walk's {x, y}[R] | s[R]
+// the herd of both walks; plain (sym false, n_jumps = 0): the walk's 64 points in its LDS layout x[64] | y[64] | s[64]; sym: the symmetric walk's
+// {x, y}[R] | s[R], keyed: with the key array of bsgs_kangaroo_setup_sym_keys
 static int kangaroo_alloc(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t n_jumps, uint32_t dp, uint32_t herd, uint32_t per_thread,
-                          uint32_t record_cap, bool keyed = false)
+                          uint32_t record_cap, bool sym, bool keyed)
 {
+    if (sym && (n_jumps < 64u || n_jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (n_jumps & (n_jumps - 1u))))
+        return fail(BSGS_ERR_ARG, "%u jump points: a power of two, 64..%u", n_jumps, BSGS_KANGAROO_SYM_MAX_JUMPS);
     const uint32_t R = n_jumps ? n_jumps : KANG_NJ;
     if (!d || !jumps_xy_le || !jump_scalars) return fail(BSGS_ERR_ARG, "null");
     if (dp > 32) return fail(BSGS_ERR_ARG, "dp %u: at most 32", dp);
@@ -424,21 +426,17 @@ static int kangaroo_alloc(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_
 extern "C" int bsgs_kangaroo_setup(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t dp, uint32_t herd, uint32_t per_thread,
                                    uint32_t record_cap)
 {
-    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, 0, dp, herd, per_thread, record_cap);
+    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, 0, dp, herd, per_thread, record_cap, false, false);
 }
 extern "C" int bsgs_kangaroo_setup_sym(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t n_jumps, uint32_t dp, uint32_t herd,
                                        uint32_t per_thread, uint32_t record_cap)
 {
-    if (n_jumps < 64u || n_jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (n_jumps & (n_jumps - 1u)))
-        return fail(BSGS_ERR_ARG, "%u jump points: a power of two, 64..%u", n_jumps, BSGS_KANGAROO_SYM_MAX_JUMPS);
-    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, n_jumps, dp, herd, per_thread, record_cap);
+    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, n_jumps, dp, herd, per_thread, record_cap, true, false);
 }
 extern "C" int bsgs_kangaroo_setup_sym_keys(bsgs_dev *d, const uint8_t *jumps_xy_le, const uint64_t *jump_scalars, uint32_t n_jumps, uint32_t dp, uint32_t herd,
                                             uint32_t per_thread, uint32_t record_cap)
 {
-    if (n_jumps < 64u || n_jumps > BSGS_KANGAROO_SYM_MAX_JUMPS || (n_jumps & (n_jumps - 1u)))
-        return fail(BSGS_ERR_ARG, "%u jump points: a power of two, 64..%u", n_jumps, BSGS_KANGAROO_SYM_MAX_JUMPS);
-    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, n_jumps, dp, herd, per_thread, record_cap, true);
+    return kangaroo_alloc(d, jumps_xy_le, jump_scalars, n_jumps, dp, herd, per_thread, record_cap, true, true);
 }
 
 static int kangaroo_put(bsgs_dev *d, const uint32_t *idx, uint32_t first, uint32_t n, const bsgs_kangaroo_state *states)
@@ -498,24 +496,26 @@ extern "C" int bsgs_kangaroo_download(bsgs_dev *d, uint32_t first, uint32_t n, b
 int bsgs_kangaroo_launch(bsgs_dev *d, uint32_t steps)
 {
     bsgs_kangaroo *k = d->kangaroo;
-    KangArgs A;
-    A.st = k->st; A.flags = k->flags; A.chain = k->chain; A.table = k->table; A.rec = k->rec;
-    A.N = k->N; A.T = k->T; A.G = k->G; A.steps = steps; A.cap = k->cap;
-    A.dp_mask = k->dp ? ~0u << (32u - k->dp) : 0u;
+    const u32 dp_mask = k->dp ? ~0u << (32u - k->dp) : 0u;
     HIPCHK(hipMemsetAsync(k->rec, 0, KANG_REC_HEADER, d->stream));
     HIPCHK(hipEventRecord(d->ev0, d->stream));
     if (k->R) {
         KangSymArgs S;
         S.st = k->st; S.flags = k->flags; S.chain = k->chain; S.table = k->table; S.rec = k->rec; S.mark = k->mark;
-        S.N = k->N; S.T = k->T; S.G = k->G; S.steps = steps; S.dp_mask = A.dp_mask; S.cap = k->cap; S.rmask = k->R - 1u;
+        S.N = k->N; S.T = k->T; S.G = k->G; S.steps = steps; S.dp_mask = dp_mask; S.cap = k->cap; S.rmask = k->R - 1u;
         S.mark_step = steps > BSGS_KANGAROO_CYCLE_WINDOW ? steps - 1u - BSGS_KANGAROO_CYCLE_WINDOW : ~0u;
         if (k->key) {
             if (k->block == 256u) hipLaunchKernelGGL(kangaroo_sym_keys_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_TABLE_OFF, d->stream, S);
             else hipLaunchKernelGGL(kangaroo_sym_keys_kernel<false>, dim3(k->T / 64u), dim3(64), 0, d->stream, S);
         } else if (k->block == 256u) hipLaunchKernelGGL(kangaroo_sym_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_TABLE_OFF, d->stream, S);
         else hipLaunchKernelGGL(kangaroo_sym_kernel<false>, dim3(k->T / 64u), dim3(64), 0, d->stream, S);
-    } else if (k->block == 256u) hipLaunchKernelGGL(kangaroo_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_LDS, d->stream, A);
-    else hipLaunchKernelGGL(kangaroo_kernel<false>, dim3(k->T / 64u), dim3(64), KANG_LDS, d->stream, A);
+    } else {
+        KangArgs A;
+        A.st = k->st; A.flags = k->flags; A.chain = k->chain; A.table = k->table; A.rec = k->rec;
+        A.N = k->N; A.T = k->T; A.G = k->G; A.steps = steps; A.dp_mask = dp_mask; A.cap = k->cap;
+        if (k->block == 256u) hipLaunchKernelGGL(kangaroo_kernel<true>, dim3(k->T / 256u), dim3(256), KANG_LDS, d->stream, A);
+        else hipLaunchKernelGGL(kangaroo_kernel<false>, dim3(k->T / 64u), dim3(64), KANG_LDS, d->stream, A);
+    }
     HIPCHK(hipGetLastError());
     return BSGS_OK;
 }

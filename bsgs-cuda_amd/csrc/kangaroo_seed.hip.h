@@ -1,6 +1,11 @@
-// kangaroo_seed.hip.h -- what the two herd seeding units share (kangaroo_seed.hip: one Q for the call; kangaroo_seed_keys.hip: one Q per key of a list): the
-// launch constants, Jacobian + affine addition and the doubling of an affine point on gfx950, and on the host the comb table, the checks of a call's
-// positions and its staging.
+// kangaroo_seed.hip.h -- what the herd seeding unit (kangaroo_seed.hip) and the verification unit (kangaroo_verify.hip) share: the launch constants,
+// Jacobian + affine addition and the doubling of an affine point on gfx950, and on the host the comb table, the checks of a call's positions and its staging.
+//
+// The comb loop itself (seventeen addends through one load and one addition site) is NOT here: it stands twice, in kangaroo_seed_keys_kernel and in
+// verify_point of kangaroo_verify.hip.  As one __forceinline__ function called from both, the seeding kernel compiles to 130 VGPRs and three waves per SIMD
+// (measured, --offload-arch=gfx950; forced to four waves: 128 VGPRs, 4 of them spilled, 16 bytes of scratch) against 128 VGPRs and four waves with its own
+// inlined loop, which is its budget (tests/test_kangaroo_seed_build.py).  The second copy is also what makes the verification an independent check of what
+// the seeding writes.
 #pragma once
 #include "bsgs_internal.h"
 #include "host_secp.h"

@@ -1,6 +1,6 @@
 // kangaroo_verify.hip -- the kangaroo counterpart of the table verification (include/bsgs_hip.h, "Kangaroo, verification": bsgs_kangaroo_verify,
 // bsgs_kangaroo_verify_points).  A kangaroo with state (x, y, d, flags) stands at sigma*Q + d*G, sigma = 0 tame, +1 wild, -1 wild with NEG: the
-// fixed-base comb of the seeding units (kangaroo_seed.hip.h: sixteen windows on |d|, y negated for d < 0, then Q of the kangaroo as a seventeenth addend, the
+// fixed-base comb of the seeding unit (kangaroo_seed.hip.h: sixteen windows on |d|, y negated for d < 0, then Q of the kangaroo as a seventeenth addend, the
 // only one that can double or cancel) computes that point again and compares.
 //   herd in place    d and flags come from the herd's own arrays, nothing crosses the bus; the comparison stays in Jacobian form, X == x Z^2 and Y == y Z^3
 //                    (four multiplications, no inversion, no LDS, no scratch per position); the herd is only read
@@ -35,7 +35,8 @@ __device__ __forceinline__ bool verify_point(fe &X, fe &Y, fe &Z, const u32x4 *c
         m3 = __builtin_subc(0u, m3, c, &co);
     }
     bool empty = true, twice = false;
-    // seventeen addends through one load and one addition site, as kangaroo_seed_keys.hip: only the last one can double or cancel
+    // seventeen addends through one load and one addition site, as kangaroo_seed_keys_kernel's own loop (two loops, not one function: shared, it costs
+    // that kernel 130 VGPRs and its fourth wave, kangaroo_seed.hip.h): only the last one can double or cancel
 #pragma nounroll
     for (u32 w = 0; w <= SEED_WINDOWS; w++) {
         const u32x4 *p;

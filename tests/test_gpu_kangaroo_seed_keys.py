@@ -1,4 +1,4 @@
-"""GPU: bsgs_kangaroo_set_keys / bsgs_kangaroo_seed_keys (csrc/kangaroo_seed_keys.hip) against the model's `start` (tests/kangaroo_model.py) with one Q per
+"""GPU: bsgs_kangaroo_set_keys / bsgs_kangaroo_seed_keys (csrc/kangaroo_seed.hip) against the model's `start` (tests/kangaroo_model.py) with one Q per
 key -- every seeded state bit for bit with flags WILD | key << 8, by range and by index list, the start that doubles Q_k and the one at infinity, one key
 against bsgs_kangaroo_seed, the error codes; then the key through the unchanged walk: every record and every downloaded state still names it."""
 import pytest

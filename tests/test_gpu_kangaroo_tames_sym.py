@@ -1,4 +1,4 @@
-"""GPU: the tame table behind a herd whose records carry a key (csrc/kangaroo_tames_keys.hip: bsgs_kangaroo_tames_install_keys, bsgs_kangaroo_run_tames_keys)
+"""GPU: the tame table behind a herd whose records carry a key (csrc/kangaroo_tames.hip: bsgs_kangaroo_tames_install_keys, bsgs_kangaroo_run_tames_keys)
 against the models (tests/kangaroo_tames_sym_model.py match, tests/kangaroo_symlist_model.py walk), bit for bit: the kept records are the walk's own, their
 `reserved` word still the key, the entry numbers in the parallel array; a table of one entry, chains that overflow their home line and wrap past the last line,
 both record capacities, and the state errors.  Herds of 256 kangaroos with 64 jump points, images of 64 lines."""

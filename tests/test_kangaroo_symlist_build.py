@@ -15,7 +15,7 @@ def rows():
         pytest.skip("no hipcc")
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import spill_report
-    return {r["kernel"]: r for r in spill_report.report(tus=["kangaroo", "kangaroo_seed_keys"])}
+    return {r["kernel"]: r for r in spill_report.report(tus=["kangaroo", "kangaroo_seed"])}
 
 
 def budget(r):
