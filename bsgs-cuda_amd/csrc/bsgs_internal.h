@@ -17,7 +17,8 @@ int bsgs_fail(int code, const char *fmt, ...);
 #define KANG_REC_HEADER 64u                                 // a record buffer (the walk's rec, the match's tames_rec): u64 count of records, then records from byte 64
 
 // kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table, the staging of a seed call and the key list;
-// kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records
+// kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records;
+// kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
     u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
@@ -39,6 +40,10 @@ struct bsgs_kangaroo {
     u32x4 *tames = nullptr;                // bsgs_kangaroo_tames_install: the image, tames_lines lines of 64 bytes (a power of two), tames_n entries
     u32 *tames_rec = nullptr;              // the records of a launch that matched, laid out as rec
     uint64_t tames_lines = 0, tames_n = 0;
+    u64 *gen_tag = nullptr;                // bsgs_kangaroo_tames_gen_begin: gen_slots tags (a power of two; 0 = empty) ...
+    u32x4 *gen_d = nullptr;                // ... and the offset of each
+    u64 *gen_ctr = nullptr;                // {entries in the table, occupied slots met by the last harvest}
+    uint64_t gen_slots = 0;
 };
 
 struct bsgs_dev {

@@ -239,5 +239,6 @@ int kangaroo_symlist_selftest(const std::vector<std::string> &args);            
 int kangaroo_symlist_roundtrip_selftest(const std::vector<std::string> &args);   // -selftest kangaroo-symlist-roundtrip: through a version-4 work file
 int kangaroo_multi_selftest(const std::vector<std::string> &args);               // -selftest kangaroo-multi: the table for a list of keys (host_kangaroo_multi.cpp)
 int kangaroo_tames_selftest(const std::vector<std::string> &args);               // -selftest kangaroo-tames: the header of a tame table file (host_kangaroo_tames.cpp)
+int kangaroo_tames_gen_selftest(const std::vector<std::string> &args);           // -selftest kangaroo-tames-gen: the rule of -ktamesgen -ktamesdev on scripted hand-backs
 int kangaroo_tames_image_selftest(const std::vector<std::string> &args);         // -selftest kangaroo-tames-image: the device image of tags read from stdin
 int kangaroo_tames_search_selftest(const std::vector<std::string> &args);        // -selftest kangaroo-tames-search: the search rule on scripted records

@@ -86,6 +86,8 @@ void usage(const Config &c)
            "-ktn T       Kangaroo -ktamesgen: entries of the table, 1..2^31\n"
            "-ktames F    Kangaroo: search -pb or every key of -infile with the tame table F of this range: all kangaroos wild, records matched against the table on the GPU\n"
            "             (the table is verified on the GPU at load, -noverify skips; not with -ksym, -kwalk sym, -wl, -dp; nothing is saved)\n"
+           "-ktamesdev   Kangaroo -ktamesgen (plain and -kwalk sym; one -d entry): the growing table is kept in GPU memory and each launch's records are inserted there; only merges,\n"
+           "             dead kangaroos and cycles come back, so -kn may be raised to the full herd (the default herd stays what the range gives); the table is verified on the GPU before it is written\n"
            "-kwalk sym   Kangaroo -ktamesgen: the tame table of the symmetric walk (file version 2; with -kjumps, -kjumpscale: default 1024 and 1)\n"
            "-ktamessym F Kangaroo: as -ktames with a table of the symmetric walk: jump points, scale and scalars come from the file (-ktames refuses such a table, and -kwalk)\n");
 }

@@ -268,6 +268,7 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-ktamesgen") c.ktamesgen = next();
         else if (a == "-ktames") { c.ktames = next(); ktames_plain = true; }
         else if (a == "-ktamessym") { c.ktames = next(); ktames_sym = true; }
+        else if (a == "-ktamesdev") c.ktamesdev = true;
         else if (a == "-ktn") { c.ktn = strtoull(next().c_str(), nullptr, 0); if (!c.ktn || c.ktn > (1ull << 31)) die("-ktn must be 1..2^31"); }
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
@@ -281,6 +282,8 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
     }
     // a tame table (host_kangaroo_tames.cpp): made by the plain walk, or with -kwalk sym by the symmetric walk (file version 2); searched with -ktames,
     // a table of the symmetric walk with -ktamessym; never saved; every refusal before any device is looked for
+    if (c.ktamesdev && c.ktamesgen.empty()) die("-ktamesdev belongs to -ktamesgen (the table that grows in GPU memory is the one being made)");
+    if (c.ktamesdev && c.devices.find(',') != std::string::npos) die("-kangaroo -ktamesgen -ktamesdev takes one -d entry (a table grown on several GPUs would have to be merged)");
     if (!c.ktamesgen.empty() || !c.ktames.empty()) {
         const std::string flag = c.ktames.empty() ? "-ktamesgen" : ktames_sym ? "-ktamessym" : "-ktames";
         if (ktames_sym && ktames_plain) die("-ktames and -ktamessym exclude each other (one table, made by one walk)");

@@ -74,6 +74,7 @@ struct KangConfig {
     bool verify = true;                            // -noverify: herds and the saved table are not checked against their offsets (at -wl, before every save)
     std::string ktamesgen, ktames;                 // -ktamesgen FILE: make a tame table; -ktames FILE: search with one (host_kangaroo_tames.cpp)
     uint64_t ktn = 0;                              // -ktn: entries of the table -ktamesgen makes
+    bool ktamesdev = false;                        // -ktamesdev with -ktamesgen: the growing table lives in device memory (bsgs_kangaroo_run_tames_gen)
     bool tames_sym = false;                        // -kwalk sym with -ktamesgen / -ktames: the table of the symmetric walk (file version 2)
 };
 KangConfig parse_kangaroo_args(int argc, char **argv);

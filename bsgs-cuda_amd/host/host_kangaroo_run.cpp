@@ -283,6 +283,7 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
             sh.parked--;
         }
     }
+    if (ok && !sh.failed.load()) { const std::string msg = mode.ending(dev, e, sh); if (!msg.empty()) end_with(msg); }
     if (dev) bsgs_dev_close(dev);
     std::lock_guard<std::mutex> lk(sh.save_m);
     sh.running--;

@@ -93,6 +93,9 @@ public:
         (void)e; (void)sh;
         return bsgs_kangaroo_run(dev, steps, recs, cap, n, dropped, nullptr);
     }
+    // in an engine's thread, after its last launch and before its device is closed (only when nothing failed): a mode that keeps something in device memory
+    // fetches it here; "", or the message the run ends with
+    virtual std::string ending(bsgs_dev *dev, uint32_t e, Shared &sh) { (void)dev; (void)e; (void)sh; return ""; }
     // what the verification needs (bsgs_kangaroo_verify, bsgs_kangaroo_verify_points; set in before_devices): the one Q of every wild kangaroo, or null: the
     // key list the engines got in setup(); why the device cannot check this search, or null; the flags a table entry's type or owner word stands for
     const uint8_t *verify_q = nullptr;

@@ -3,6 +3,9 @@
 //   bsgs_mi355x -kangaroo -ktamesgen FILE -ktn T   an all-tame herd walks until the host's map holds T distinguished points, which are written sorted
 //   bsgs_mi355x -kangaroo -ktames FILE             an all-wild herd, shared over the keys, walks with the file's jumps; each launch's records are matched
 //                                                 against the table on the device (bsgs_kangaroo_run_tames) and only the matches come back
+//   bsgs_mi355x -kangaroo -ktamesgen FILE -ktn T -ktamesdev   the same herd, the growing table in device memory (include/bsgs_hip.h "Kangaroo, tame table grown
+//                                                 on the device"): each launch's records are inserted there (bsgs_kangaroo_run_tames_gen) and only merges, dead
+//                                                 kangaroos and cycles come back; GenRule is what they mean, without a device (-selftest kangaroo-tames-gen)
 // Neither writes kangaroo.work.  TamesRule is the search rule without a device: -selftest kangaroo-tames-search drives it with scripted records.
 // -ktamesgen -kwalk sym and -ktamessym FILE run the symmetric walk (include/bsgs_hip.h "Kangaroo, tame table for the symmetric walk"; tests/kangaroo_tames_sym_model.py): the
 // file is version 2 (R, the jump scale and R scalars), offsets are counted from the middle of the range and are those of representatives, the search's herd is
@@ -209,9 +212,42 @@ u128 range_width(const Scalar &lo, const Scalar &hi)
     return (((u128)wm1.l[1] << 64) | wm1.l[0]) + 1;
 }
 
+// ---- -ktamesgen -ktamesdev: what a handed-back record means, without a device ----------------------------------------------------------------------------
+class GenRule {
+public:
+    enum What { RESEED, MERGE, HELD, DROPPED, IGNORED };
+    explicit GenRule(uint64_t T) : T_(T) {}
+    void entries(uint64_t n) { dev_ = n; }                            // entries in the device's table after a launch
+    uint64_t total() const { return dev_ + held_.size(); }
+    bool done() const { return total() >= T_; }
+    // one record the device handed back, `reason` its reserved word (BSGS_KANGAROO_GEN_*): a dead kangaroo starts afresh; a duplicate has merged into a
+    // known trail and starts afresh; the one tag the device cannot hold is kept here, where a second one is a merge; FULL is counted (the sizing makes
+    // it unreachable).  Once the table is done nothing is looked at
+    What record(uint32_t reason, uint64_t x, i128 d)
+    {
+        if (done()) return IGNORED;
+        switch (reason) {
+            case BSGS_KANGAROO_GEN_DEAD: reseeds_++; return RESEED;
+            case BSGS_KANGAROO_GEN_DUPLICATE: merges_++; reseeds_++; return MERGE;
+            case BSGS_KANGAROO_GEN_TAG_ZERO:
+                if (!held_.emplace(x, d).second) { merges_++; reseeds_++; return MERGE; }
+                return HELD;
+            default: dropped_++; return DROPPED;
+        }
+    }
+    const std::map<uint64_t, i128> &held() const { return held_; }
+    uint64_t merges() const { return merges_; }
+    uint64_t reseeds() const { return reseeds_; }
+    uint64_t dropped() const { return dropped_; }
+private:
+    const uint64_t T_;
+    uint64_t dev_ = 0, merges_ = 0, reseeds_ = 0, dropped_ = 0;
+    std::map<uint64_t, i128> held_;
+};
+
 // ---- -ktamesgen ---------------------------------------------------------------------------------------------------------------------------------------
 struct GenMode : Mode {
-    GenMode(const KangConfig &c, const Prologue &p) : c(c), T(c.ktn)
+    GenMode(const KangConfig &c, const Prologue &p) : c(c), T(c.ktn), rule(c.ktn)
     {
         saves = false;
         // dp: the command line's, else about (log2(W / T)) / 2 - 4: the trails stay a small part of the range while a wild walk to the next DP stays short
@@ -226,7 +262,7 @@ struct GenMode : Mode {
             jumpscale = c.jumpscale != 0.0 ? c.jumpscale : 1.0;
             min_launch = 2.0 * BSGS_KANGAROO_CYCLE_WINDOW;
         }
-        map.reserve((size_t)T * 2);
+        if (!c.ktamesdev) map.reserve((size_t)T * 2);
     }
     // -kwalk sym: the mean jump depends on the steps a kangaroo of this herd walks; mean -kjumpscale * m, starts in [1, ceil(W/2) + E)
     void planned(const Prologue &p) override
@@ -241,8 +277,10 @@ struct GenMode : Mode {
     const char *setup(bsgs_dev *dev) override
     {
         const Plan &pl = pro->pl;
-        if (c.tames_sym) return bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) == BSGS_OK ? nullptr : "bsgs_kangaroo_setup_sym";
-        return bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) == BSGS_OK ? nullptr : "bsgs_kangaroo_setup";
+        if (c.tames_sym) { if (bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup_sym"; }
+        else if (bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup";
+        if (c.ktamesdev && bsgs_kangaroo_tames_gen_begin(dev, T) != BSGS_OK) return "bsgs_kangaroo_tames_gen_begin";
+        return nullptr;
     }
     // every kangaroo is tame: t uniform in [1, W + E), with -kwalk sym in [1, ceil(W/2) + E), d = t
     const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) override
@@ -256,8 +294,75 @@ struct GenMode : Mode {
         if (ninf) sh.push_reseed(e, idx.empty() ? first : idx[first]);
         return nullptr;
     }
+    // -ktamesdev: the launch, the insert on the device, the handed-back records alone; the entry count decides when the table is done
+    int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &sh) override
+    {
+        if (!c.ktamesdev) return Mode::launch(dev, e, steps, recs, cap, n, dropped, sh);
+        uint64_t n_seen = 0, n_entries = 0;
+        const int rc = bsgs_kangaroo_run_tames_gen(dev, steps, recs, cap, n, &n_seen, &n_entries, dropped, nullptr);
+        if (rc != BSGS_OK) return rc;
+        seen += n_seen;
+        std::lock_guard<std::mutex> lt(sh.tab_m);
+        rule.entries(n_entries);
+        if (rule.done()) sh.stop = true;
+        return rc;
+    }
+    // -ktamesdev, in the engine's thread before its device is closed: the finished table leaves the device, takes the host's entries in, is sorted and cut
+    // to the T lowest tags, and every entry that will be written is checked against d*G on this engine
+    std::string ending(bsgs_dev *dev, uint32_t, Shared &sh) override
+    {
+        if (!c.ktamesdev) return "";
+        std::lock_guard<std::mutex> lt(sh.tab_m);
+        if (!rule.done()) return "";
+        walked = since(pro->t0);
+        uint64_t n = 0;
+        (void)bsgs_kangaroo_tames_gen_read(dev, nullptr, nullptr, 0, &n);      // the count alone
+        std::vector<uint64_t> x((size_t)n);
+        std::vector<i128> d((size_t)n);
+        if (n && bsgs_kangaroo_tames_gen_read(dev, x.data(), (uint8_t *)d.data(), n, &n) != BSGS_OK) return std::string("bsgs_kangaroo_tames_gen_read: ") + bsgs_last_error();
+        table.reserve((size_t)n + rule.held().size());
+        for (uint64_t i = 0; i < n; i++) table.emplace_back(x[i], d[i]);
+        std::vector<uint64_t>().swap(x);
+        std::vector<i128>().swap(d);
+        for (const auto &kv : rule.held()) table.push_back(kv);
+        if (table.size() < T) return "growing tame table: " + std::to_string(table.size()) + " entries read, " + std::to_string(T) + " counted";
+        std::sort(table.begin(), table.end());
+        table.resize((size_t)T);
+        (void)bsgs_kangaroo_tames_gen_end(dev);
+        if (!c.verify) return "";
+        const auto ts = Clock::now();
+        uint8_t g[64];
+        hs::affine_to_le(hs::G, g, g + 32);
+        const uint64_t step = 1u << 20;
+        std::vector<uint32_t> fl((size_t)std::min(T, step), 0u);
+        x.resize(fl.size()); d.resize(fl.size());
+        for (uint64_t pos = 0; pos < T; pos += step) {
+            const uint32_t m = (uint32_t)std::min(T - pos, step);
+            for (uint32_t k = 0; k < m; k++) { x[k] = table[pos + k].first; d[k] = table[pos + k].second; }
+            uint32_t n_bad = 0, first = 0;
+            if (bsgs_kangaroo_verify_points(dev, g, m, (const uint8_t *)d.data(), fl.data(), x.data(), &n_bad, &first, 1) != BSGS_OK)
+                return std::string("bsgs_kangaroo_verify_points: ") + bsgs_last_error();
+            if (n_bad) { table.clear(); return "Tame table is damaged: entry " + std::to_string(pos + first) + " does not match its offset"; }
+        }
+        printf("\n[verify] tame table: %llu entries %.3fs\n", (unsigned long long)T, since(ts));
+        return "";
+    }
+    bool record_dev(uint32_t e, const bsgs_kangaroo_record &r, Shared &sh)
+    {
+        uint64_t x; i128 d;
+        memcpy(&x, r.x, 8); memcpy(&d, r.d, 16);
+        handed_back++;
+        switch (rule.record(r.reserved, x, d)) {
+            case GenRule::IGNORED: return false;
+            case GenRule::RESEED: case GenRule::MERGE: sh.push_reseed(e, r.kangaroo); break;
+            case GenRule::HELD: if (rule.done()) { sh.stop = true; return false; } break;
+            case GenRule::DROPPED: sh.dropped++; break;
+        }
+        return true;
+    }
     bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &sh) override
     {
+        if (c.ktamesdev) return record_dev(e, r, sh);
         if (map.size() >= T) return false;
         if (r.flags & BSGS_KANGAROO_DEAD) { sh.push_reseed(e, r.kangaroo); return true; }
         uint64_t x; i128 d;
@@ -267,10 +372,17 @@ struct GenMode : Mode {
         return true;
     }
     uint32_t entry_flags(uint32_t) const override { return 0u; }
-    bool done() const override { return map.size() >= T; }
+    size_t size() const { return c.ktamesdev ? (size_t)rule.total() : map.size(); }
+    uint64_t n_merges() const { return c.ktamesdev ? rule.merges() : merges; }
+    bool done() const override { return size() >= T; }
     bool give_up(uint64_t steps) override { return (double)steps > 50.0 * pro->pl.expected; }
     void status(double rate, uint64_t st, uint64_t dps) const override
     {
+        if (c.ktamesdev) {
+            printf("\r[%u] %.3e steps/s  steps 2^%.2f  entries %zu of %llu  DPs %llu  handed back %llu  merges %llu  %.0fs   ", pro->pl.engines, rate, st ? std::log2((double)st) : 0.0, size(),
+                   (unsigned long long)T, (unsigned long long)seen.load(), (unsigned long long)handed_back, (unsigned long long)rule.merges(), since(pro->t0));
+            return;
+        }
         printf("\r[%u] %.3e steps/s  steps 2^%.2f  entries %zu of %llu  DPs %llu  merges %llu  %.0fs   ", pro->pl.engines, rate, st ? std::log2((double)st) : 0.0, map.size(),
                (unsigned long long)T, (unsigned long long)dps, (unsigned long long)merges, since(pro->t0));
     }
@@ -283,6 +395,13 @@ struct GenMode : Mode {
     u128 span;
     std::unordered_map<uint64_t, i128> map;
     uint64_t merges = 0;
+    // -ktamesdev: the rule of the handed-back records (under sh.tab_m), the records the walk produced, the records that crossed the bus, and the
+    // finished table: the T lowest tags, sorted (ending())
+    GenRule rule;
+    std::atomic<uint64_t> seen{0};
+    uint64_t handed_back = 0;
+    std::vector<std::pair<uint64_t, i128>> table;
+    double walked = 0.0;                                               // seconds from the start to the launch that completed the table
 };
 
 int tames_generate(const KangConfig &c)
@@ -300,21 +419,28 @@ int tames_generate(const KangConfig &c)
     const double secs = since(p.t0);
     if (o != DONE) {
         printf("\nKangaroo: tame table not finished after %llu steps (%s), %zu of %llu entries; nothing written\n", (unsigned long long)sh.steps.load(),
-               o == GAVE_UP ? "the trails have saturated the range: a smaller -ktn or -dp" : o == BUDGET ? "-ksteps" : "signal", mode.map.size(), (unsigned long long)c.ktn);
+               o == GAVE_UP ? "the trails have saturated the range: a smaller -ktn or -dp" : o == BUDGET ? "-ksteps" : "signal", mode.size(), (unsigned long long)c.ktn);
         return o == GAVE_UP ? 1 : 3;
     }
     TamesFile f;
     f.dp = p.pl.dp; f.lo = p.lo; f.hi = p.hi; f.steps = sh.steps.load(); f.seed = p.wh.seed; f.m = mode.plan.m; f.js = p.js;
     if (c.tames_sym) { f.version = TAMES_VERSION_SYM; f.R = mode.jumps; f.jumpscale = mode.jumpscale; f.m = (uint64_t)mode.mean_jump; }
-    std::vector<std::pair<uint64_t, i128>> en(mode.map.begin(), mode.map.end());
-    std::sort(en.begin(), en.end());
-    en.resize((size_t)c.ktn);
+    std::vector<std::pair<uint64_t, i128>> en;
+    if (c.ktamesdev) en.swap(mode.table);                              // read, completed, sorted, cut and verified in the engine's thread (GenMode::ending)
+    else {
+        en.assign(mode.map.begin(), mode.map.end());
+        std::sort(en.begin(), en.end());
+        en.resize((size_t)c.ktn);
+    }
+    if (en.size() != c.ktn) die("tame table: " + std::to_string(en.size()) + " entries of " + std::to_string(c.ktn));
     for (const auto &kv : en) { f.x.push_back(kv.first); f.d.push_back(kv.second); }
     std::string path = c.ktamesgen;
     if (path.find('/') == std::string::npos) path = c.dir + "/" + path;
     if (!write_tames(path, f)) die("cannot write " + path);
-    printf("\nTame table %s: %llu entries, %.3e steps, %llu DPs, %llu merges, %.2fs\n", path.c_str(), (unsigned long long)c.ktn, (double)f.steps, (unsigned long long)sh.dps.load(),
-           (unsigned long long)mode.merges, secs);
+    printf("\nTame table %s: %llu entries, %.3e steps, %llu DPs, %llu merges, %.2fs\n", path.c_str(), (unsigned long long)c.ktn, (double)f.steps,
+           (unsigned long long)(c.ktamesdev ? mode.seen.load() : sh.dps.load()), (unsigned long long)mode.n_merges(), secs);
+    if (c.ktamesdev) printf("Table grown on the GPU: %llu records inserted there, %llu handed back over the bus (%llu dropped), %.2fs of walking\n", (unsigned long long)mode.seen.load(),
+                            (unsigned long long)mode.handed_back, (unsigned long long)sh.dropped.load(), mode.walked);
     fflush(stdout);
     return 0;
 }
@@ -587,6 +713,42 @@ int kangaroo_tames_selftest(const std::vector<std::string> &args)
         if (hs::fe_cmp(lo, f.lo) != 0 || hs::fe_cmp(hi, f.hi) != 0) { fprintf(stderr, "Tame table was made for another range\n"); return 1; }
     }
     printf("ok\n");
+    return 0;
+}
+
+// -selftest kangaroo-tames-gen <T> <item>...: the rule of -ktamesgen -ktamesdev on scripted hand-backs, no GPU.
+//   D|U|Z|F,<x hex>,<d hex: 128-bit two's complement>,<kangaroo>   a record the device handed back as DEAD, DUPLICATE, TAG_ZERO or FULL
+//   E,<n>                                                          the device's table holds n entries after this launch
+// One line per item: "reseed <kangaroo>", "merge <kangaroo>" (it starts afresh too), "held <kangaroo>" (the host keeps the entry), "dropped", "ignored" (the
+// table was done), "entries <device + host>"; "done" once after the item that completes the table; then "summary <re-seeds> <merges> <held> <dropped> <done>".
+int kangaroo_tames_gen_selftest(const std::vector<std::string> &a)
+{
+    if (a.empty()) return 2;
+    const uint64_t T = strtoull(a[0].c_str(), nullptr, 0);
+    if (!T || T > (1ull << 31)) return 2;
+    GenRule rule(T);
+    bool said = false;
+    for (size_t i = 1; i < a.size(); i++) {
+        const std::vector<std::string> t = split_commas(a[i]);
+        if (t.size() == 2 && t[0] == "E") {
+            rule.entries(strtoull(t[1].c_str(), nullptr, 0));
+            printf("entries %llu\n", (unsigned long long)rule.total());
+        } else if (t.size() == 4 && t[0].size() == 1 && strchr("DUZF", t[0][0])) {
+            Scalar x, dd;
+            if (!hs::fe_from_hex(x, t[1]) || !hs::fe_from_hex(dd, t[2]) || dd.l[2] || dd.l[3]) return 2;
+            const unsigned long long kid = strtoull(t[3].c_str(), nullptr, 10);
+            const uint32_t reason = t[0] == "D" ? BSGS_KANGAROO_GEN_DEAD : t[0] == "U" ? BSGS_KANGAROO_GEN_DUPLICATE : t[0] == "Z" ? BSGS_KANGAROO_GEN_TAG_ZERO : BSGS_KANGAROO_GEN_FULL;
+            switch (rule.record(reason, x.l[0], (i128)(((u128)dd.l[1] << 64) | dd.l[0]))) {
+                case GenRule::RESEED: printf("reseed %llu\n", kid); break;
+                case GenRule::MERGE: printf("merge %llu\n", kid); break;
+                case GenRule::HELD: printf("held %llu\n", kid); break;
+                case GenRule::DROPPED: printf("dropped\n"); break;
+                case GenRule::IGNORED: printf("ignored\n"); break;
+            }
+        } else return 2;
+        if (rule.done() && !said) { printf("done\n"); said = true; }
+    }
+    printf("summary %llu %llu %zu %llu %d\n", (unsigned long long)rule.reseeds(), (unsigned long long)rule.merges(), rule.held().size(), (unsigned long long)rule.dropped(), rule.done() ? 1 : 0);
     return 0;
 }
 

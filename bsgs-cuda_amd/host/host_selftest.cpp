@@ -147,6 +147,8 @@ int selftest(int argc, char **argv)
             return kangaroo_symlist_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-symlist") {                            // the same table on a scripted record stream (host_kangaroo_symlist.cpp)
             return kangaroo_symlist_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-tames-gen") {                          // the rule of -ktamesgen -ktamesdev on scripted hand-backs (no GPU)
+            return kangaroo_tames_gen_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-tames-image") {                        // the device image of a tame table (host_kangaroo_tames.cpp; no GPU)
             return kangaroo_tames_image_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-tames-search") {                       // the search rule of -ktames on scripted records

@@ -30,6 +30,7 @@ NATIVE_SYMBOLS = [
     "bsgs_kangaroo_setup", "bsgs_kangaroo_upload", "bsgs_kangaroo_upload_list", "bsgs_kangaroo_download", "bsgs_kangaroo_run", "bsgs_kangaroo_geometry", "bsgs_kangaroo_seed", "bsgs_kangaroo_setup_sym", "bsgs_kangaroo_setup_sym_keys",
     "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_kangaroo_verify", "bsgs_kangaroo_verify_points", "bsgs_selftest_fe3",
     "bsgs_kangaroo_tames_image", "bsgs_kangaroo_tames_install", "bsgs_kangaroo_run_tames", "bsgs_kangaroo_tames_install_keys", "bsgs_kangaroo_run_tames_keys",
+    "bsgs_kangaroo_tames_gen_begin", "bsgs_kangaroo_run_tames_gen", "bsgs_kangaroo_tames_gen_insert", "bsgs_kangaroo_tames_gen_read", "bsgs_kangaroo_tames_gen_end",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
@@ -75,6 +76,7 @@ FE3_INV_BLOCK_KANG, FE3_INV_BLOCK_SEED, FE3_INV_BLOCK_TILE, FE3_INV_BLOCK2_TILE,
 
 KANGAROO_JUMPS, KANGAROO_WILD, KANGAROO_DEAD = 64, 1, 0x80000000
 KANGAROO_NEG, KANGAROO_CYCLE = 2, 4                # the symmetric walk (kangaroo_setup_sym)
+KANGAROO_GEN_DEAD, KANGAROO_GEN_DUPLICATE, KANGAROO_GEN_TAG_ZERO, KANGAROO_GEN_FULL = range(4)   # why the growing tame table hands a record back
 KANGAROO_KEY_SHIFT, KANGAROO_MAX_KEYS = 8, 65535   # many keys in one herd (kangaroo_set_keys): a wild kangaroo's key index, 16 bits of its flags
 
 _lib = None
@@ -195,6 +197,12 @@ def lib():
             "bsgs_kangaroo_tames_install": [vp, C.POINTER(C.c_uint64), C.c_uint64],
             "bsgs_kangaroo_run_tames": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
             "bsgs_kangaroo_tames_install_keys": [vp, C.POINTER(C.c_uint64), C.c_uint64],
+            "bsgs_kangaroo_tames_gen_begin": [vp, C.c_uint64],
+            "bsgs_kangaroo_run_tames_gen": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_float)],
+            "bsgs_kangaroo_tames_gen_insert": [vp, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+            "bsgs_kangaroo_tames_gen_read": [vp, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64)],
+            "bsgs_kangaroo_tames_gen_end": [vp],
             "bsgs_kangaroo_run_tames_keys": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_float)],
         }
@@ -761,6 +769,57 @@ class Device:
         out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
                 "key": r.reserved, "entry": e - 1 if e else None} for r, e in zip(recs[:n.value], ent[:n.value])]
         return out, seen.value, dropped.value, ms.value
+
+    # ---- the tame table grown on the device (include/bsgs_hip.h "Kangaroo, tame table grown on the device")
+    def kangaroo_tames_gen_begin(self, capacity):
+        """allocates the growing table for `capacity` entries under the herd of kangaroo_setup / kangaroo_setup_sym; replaces an earlier one"""
+        _chk(self.L.bsgs_kangaroo_tames_gen_begin(self.h, capacity))
+
+    @staticmethod
+    def _gen_handed_back(recs, n):
+        return [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
+                 "reason": r.reserved} for r in recs[:n]]
+
+    def kangaroo_run_tames_gen(self, steps, max_recs=None):
+        """one launch of `steps` steps inserted into the growing table on the device: (handed-back records, n_seen, n_entries, dropped, kernel ms); a
+        handed-back record is kangaroo_run's with "reason" (KANGAROO_GEN_*) in the place of "key" """
+        cap = max(1, self._kang_cap if max_recs is None else max_recs)
+        recs = (KangarooRecord * cap)()
+        n, seen, entries, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _chk(self.L.bsgs_kangaroo_run_tames_gen(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
+        return self._gen_handed_back(recs, n.value), seen.value, entries.value, dropped.value, ms.value
+
+    def kangaroo_tames_gen_insert(self, records):
+        """the insert alone on records of the caller's, (tag or x, d, flags[, kangaroo]) each: (handed-back records, n_entries)"""
+        m = len(records)
+        arr = (KangarooRecord * max(1, m))()
+        for k, (x, d, fl, *kang) in enumerate(records):
+            arr[k].x[:] = le32(x)
+            arr[k].d[:] = (d % (1 << 128)).to_bytes(16, "little")
+            arr[k].flags = fl
+            arr[k].kangaroo = kang[0] if kang else k
+        cap = max(1, self._kang_cap)
+        out = (KangarooRecord * cap)()
+        n, entries = C.c_uint32(), C.c_uint64()
+        _chk(self.L.bsgs_kangaroo_tames_gen_insert(self.h, arr, m, out, cap, C.byref(n), C.byref(entries)))
+        return self._gen_handed_back(out, n.value), entries.value
+
+    def kangaroo_tames_gen_read(self, max_entries=None):
+        """the table's entries as a list of (tag, d mod 2^128), in any order; max_entries: the room offered (None: what the table holds)"""
+        n = C.c_uint64()
+        if max_entries is None:
+            rc = self.L.bsgs_kangaroo_tames_gen_read(self.h, None, None, 0, C.byref(n))
+            if n.value == 0:
+                _chk(rc)
+                return []
+            max_entries = n.value
+        tags, d = (C.c_uint64 * max(1, max_entries))(), C.create_string_buffer(16 * max(1, max_entries))
+        _chk(self.L.bsgs_kangaroo_tames_gen_read(self.h, tags, d, max_entries, C.byref(n)))
+        raw = d.raw
+        return [(tags[k], int.from_bytes(raw[16 * k:16 * k + 16], "little")) for k in range(n.value)]
+
+    def kangaroo_tames_gen_end(self):
+        _chk(self.L.bsgs_kangaroo_tames_gen_end(self.h))
 
     def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):
         """start points on the GPU: kangaroo idx[k] (first + k without idx) := (d*G or Q + d*G, d, flags[k]) for d = offsets[k] (a signed integer) and

@@ -2,7 +2,7 @@
 """Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
-    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--no-vgprs] [--out FILE]
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--no-vgprs] [--out FILE]
 
 --sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch); with --keys
 the herd of bsgs_kangaroo_setup_sym_keys, whose kernel entry point reads a kangaroo's key when it writes a record (keys 0..15 dealt out over the herd).
@@ -10,6 +10,10 @@ the herd of bsgs_kangaroo_setup_sym_keys, whose kernel entry point reads a kanga
 --tames N installs a tame table of N entries (bsgs_kangaroo_tames_install; tags that no record meets, so every lookup ends in a miss, as all but a handful
 do in a search) and times bsgs_kangaroo_run_tames and bsgs_kangaroo_run in turn, launch by launch: the difference of their kernel times is the match.
 With --sym --keys the table is that of the keyed herd (bsgs_kangaroo_tames_install_keys, bsgs_kangaroo_run_tames_keys: the search of -ktamessym).
+
+--tamesgen N begins a growing tame table of capacity N (bsgs_kangaroo_tames_gen_begin) under an all-tame herd of pairwise different starts (seeded on the
+GPU: repeated starts would make every record a duplicate) and times bsgs_kangaroo_run_tames_gen and bsgs_kangaroo_run in turn, launch by launch, in one
+process: the difference of their kernel times is the insert.  Plain walk, or with --sym the symmetric one (the generators of -ktamesgen -ktamesdev).
 
 The starts are 65536 distinct points P0 + i*G, repeated over the herd (the walk's cost does not depend on which point a kangaroo stands on; repeats only
 make their DPs coincide)."""
@@ -56,11 +60,14 @@ def main():
     ap.add_argument("--jumps", type=int, default=1024)
     ap.add_argument("--keys", action="store_true")
     ap.add_argument("--tames", type=int, default=0)
+    ap.add_argument("--tamesgen", type=int, default=0)
     ap.add_argument("--no-vgprs", action="store_true", help="do not compile the walk's unit for its VGPR count")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.keys and not a.sym:
         ap.error("--keys goes with --sym")
+    if a.tamesgen and (a.keys or a.tames):
+        ap.error("--tamesgen goes with the plain walk or --sym alone")
     dev = pybsgs.Device(0)
     L = dev.L
     cus = C.c_int()
@@ -89,6 +96,47 @@ def main():
     def launch():
         pybsgs._chk(L.bsgs_kangaroo_run(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(dropped), C.byref(ms)))
         return ms.value, cnt.value + dropped.value
+
+    if a.tamesgen:
+        import numpy as np
+        d = np.random.RandomState(7).randint(1, 1 << 62, size=(n, 2), dtype=np.uint64)
+        d[:, 1] &= np.uint64((1 << 36) - 1)                          # tame offsets below 2^100, pairwise different but for a 2^-62 chance
+        flags = (C.c_uint32 * n)()
+        pybsgs._chk(L.bsgs_kangaroo_seed(dev.h, None, None, 0, n, d.tobytes(), flags, None, None))
+        t0 = time.perf_counter()
+        pybsgs._chk(L.bsgs_kangaroo_tames_gen_begin(dev.h, a.tamesgen))
+        begin_s = time.perf_counter() - t0
+        seen, n_entries = C.c_uint64(), C.c_uint64()
+
+        def launch_gen():
+            pybsgs._chk(L.bsgs_kangaroo_run_tames_gen(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(n_entries), C.byref(dropped), C.byref(ms)))
+            return ms.value, seen.value, cnt.value
+
+        for _ in range(a.warmup):
+            launch()
+            launch_gen()
+        plain, both, nrec, back, dr = [], [], 0, 0, 0
+        for _ in range(a.launches):
+            plain.append(launch()[0])
+            k, r, m = launch_gen()
+            both.append(k)
+            nrec += r
+            back += m
+            dr += dropped.value
+        ins = (sum(both) - sum(plain)) / len(both)
+        res = {"what": "kangaroo walk with the tame table grown on the device, one engine, full herd, all tame" + (", symmetric walk" if a.sym else ""), "gpu": dev.name(), "kangaroos": n,
+               "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp, "launches": a.launches, "capacity": a.tamesgen, "begin_s": begin_s,
+               "ms_per_launch_walk": sum(plain) / len(plain), "ms_per_launch_walk_and_insert": sum(both) / len(both), "ms_insert": ins, "insert_share": ins / (sum(both) / len(both)),
+               "ms_walk_each": plain, "ms_walk_and_insert_each": both,
+               "records_per_launch": nrec / a.launches, "records_handed_back_per_launch": back / a.launches, "dropped": dr, "entries": n_entries.value,
+               "steps_per_s_kernel_walk": n * a.steps / (sum(plain) / len(plain) / 1e3), "steps_per_s_kernel_walk_and_insert": n * a.steps / (sum(both) / len(both) / 1e3)}
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        dev.close()
+        return
 
     if a.tames:
         import numpy as np
