@@ -18,7 +18,7 @@ int bsgs_fail(int code, const char *fmt, ...);
 
 // kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table, the staging of a seed call and the key list;
 // kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records;
-// kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer
+// kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer; kangaroo_tames_extend.hip: its load and sorted read
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
     u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
@@ -42,7 +42,7 @@ struct bsgs_kangaroo {
     uint64_t tames_lines = 0, tames_n = 0;
     u64 *gen_tag = nullptr;                // bsgs_kangaroo_tames_gen_begin: gen_slots tags (a power of two; 0 = empty) ...
     u32x4 *gen_d = nullptr;                // ... and the offset of each
-    u64 *gen_ctr = nullptr;                // {entries in the table, occupied slots met by the last harvest}
+    u64 *gen_ctr = nullptr;                // eight words: entries in the table, occupied slots met by the last harvest; kangaroo_tames_extend.hip: the four counts of a load, OR and AND of the tags
     uint64_t gen_slots = 0;
 };
 

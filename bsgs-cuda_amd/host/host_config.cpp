@@ -88,6 +88,11 @@ void usage(const Config &c)
            "             (the table is verified on the GPU at load, -noverify skips; not with -ksym, -kwalk sym, -wl, -dp; nothing is saved)\n"
            "-ktamesdev   Kangaroo -ktamesgen (plain and -kwalk sym; one -d entry): the growing table is kept in GPU memory and each launch's records are inserted there; only merges,\n"
            "             dead kangaroos and cycles come back, so -kn may be raised to the full herd (the default herd stays what the range gives); the table is verified on the GPU before it is written\n"
+           "-ktamesfrom F Kangaroo -ktamesgen OUT -ktamesdev -ktn T: extend the table F to T entries: dp, range, jumps and scalars come from F, its entries are loaded into GPU memory\n"
+           "             and a new herd (another -kseed) walks until T are there; OUT may be F\n"
+           "-ktnplan N   Kangaroo -ktamesgen: plan the walk (mean jump, default -dp) for a table of N entries, N at least -ktn: for a table that will be extended or merged later\n"
+           "-ktamesmerge A,B[,C...] Kangaroo -ktamesgen OUT [-ktn T] [-kwalk sym]: merge tables of one walk by tag on the host, one entry per tag (the first table that has it);\n"
+           "             -ktn keeps the T lowest tags; every entry written is verified on the first -d device unless -noverify (then no GPU is opened)\n"
            "-kwalk sym   Kangaroo -ktamesgen: the tame table of the symmetric walk (file version 2; with -kjumps, -kjumpscale: default 1024 and 1)\n"
            "-ktamessym F Kangaroo: as -ktames with a table of the symmetric walk: jump points, scale and scalars come from the file (-ktames refuses such a table, and -kwalk)\n");
 }

@@ -256,8 +256,8 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-h") { usage(Config()); exit(0); }
         else if (a == "-pb") { c.pub = cut_hex(next()); c.pub_given = true; }
         else if (a == "-infile") c.infile = next();
-        else if (a == "-pk") c.pk = cut_hex(next());
-        else if (a == "-pke") c.pke = cut_hex(next());
+        else if (a == "-pk") { c.pk = cut_hex(next()); c.range_given = true; }
+        else if (a == "-pke") { c.pke = cut_hex(next()); c.range_given = true; }
         else if (a == "-d") c.devices = next();
         else if (a == "-dir") c.dir = next();
         else if (a == "-dp") { c.dp = atoi(next().c_str()); if (c.dp < 0 || c.dp > 32) die("-dp must be 0..32"); }
@@ -269,6 +269,9 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-ktames") { c.ktames = next(); ktames_plain = true; }
         else if (a == "-ktamessym") { c.ktames = next(); ktames_sym = true; }
         else if (a == "-ktamesdev") c.ktamesdev = true;
+        else if (a == "-ktamesfrom") c.ktamesfrom = next();
+        else if (a == "-ktamesmerge") c.ktamesmerge = next();
+        else if (a == "-ktnplan") { c.ktnplan = strtoull(next().c_str(), nullptr, 0); if (!c.ktnplan || c.ktnplan > (1ull << 31)) die("-ktnplan must be 1..2^31"); }
         else if (a == "-ktn") { c.ktn = strtoull(next().c_str(), nullptr, 0); if (!c.ktn || c.ktn > (1ull << 31)) die("-ktn must be 1..2^31"); }
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
@@ -284,6 +287,15 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
     // a table of the symmetric walk with -ktamessym; never saved; every refusal before any device is looked for
     if (c.ktamesdev && c.ktamesgen.empty()) die("-ktamesdev belongs to -ktamesgen (the table that grows in GPU memory is the one being made)");
     if (c.ktamesdev && c.devices.find(',') != std::string::npos) die("-kangaroo -ktamesgen -ktamesdev takes one -d entry (a table grown on several GPUs would have to be merged)");
+    // extending a table (-ktamesfrom), planning for its final size (-ktnplan), merging tables (-ktamesmerge): all three belong to -ktamesgen
+    if (!c.ktamesfrom.empty() && (c.ktamesgen.empty() || !c.ktamesdev)) die("-ktamesfrom belongs to -ktamesgen -ktamesdev (a table is extended in GPU memory)");
+    if (c.ktnplan && c.ktamesgen.empty()) die("-ktnplan belongs to -ktamesgen");
+    if (c.ktnplan && !c.ktamesfrom.empty()) die("-ktnplan cannot be combined with -ktamesfrom (the walk comes from the table that is extended)");
+    if (c.ktnplan && c.ktnplan < c.ktn) die("-ktnplan must not be below -ktn (it is the size the table is meant to reach)");
+    if (!c.ktamesmerge.empty()) {
+        if (c.ktamesgen.empty()) die("-ktamesmerge belongs to -ktamesgen (the file the merged table is written to)");
+        if (c.ktamesdev || !c.ktamesfrom.empty() || c.ktnplan) die("-ktamesmerge cannot be combined with -ktamesdev, -ktamesfrom or -ktnplan (tables are merged on the host, nothing walks)");
+    }
     if (!c.ktamesgen.empty() || !c.ktames.empty()) {
         const std::string flag = c.ktames.empty() ? "-ktamesgen" : ktames_sym ? "-ktamessym" : "-ktames";
         if (ktames_sym && ktames_plain) die("-ktames and -ktamessym exclude each other (one table, made by one walk)");
@@ -295,7 +307,7 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         if (!c.wl.empty()) die("-kangaroo " + flag + " cannot be combined with -wl (nothing is saved, so nothing is resumed)");
         if (c.ktames.empty()) {
             if (wt_given) die("-kangaroo -ktamesgen cannot be combined with -wt (nothing is saved but the table)");
-            if (!c.ktn) die("-kangaroo -ktamesgen needs -ktn (the entries of the table)");
+            if (!c.ktn && c.ktamesmerge.empty()) die("-kangaroo -ktamesgen needs -ktn (the entries of the table)");
             if (c.pub_given || !c.infile.empty()) die("-kangaroo -ktamesgen takes no -pb or -infile (a tame table serves every key of its range)");
         } else {
             if (c.dp >= 0) die("-kangaroo " + flag + " cannot be combined with -dp (the table names its own)");

@@ -76,6 +76,10 @@ struct KangConfig {
     uint64_t ktn = 0;                              // -ktn: entries of the table -ktamesgen makes
     bool ktamesdev = false;                        // -ktamesdev with -ktamesgen: the growing table lives in device memory (bsgs_kangaroo_run_tames_gen)
     bool tames_sym = false;                        // -kwalk sym with -ktamesgen / -ktames: the table of the symmetric walk (file version 2)
+    std::string ktamesfrom;                        // -ktamesfrom IN with -ktamesgen -ktamesdev: IN is loaded into the growing table and extended to -ktn entries
+    std::string ktamesmerge;                       // -ktamesmerge A,B[,C...] with -ktamesgen: the tables are merged by tag on the host
+    uint64_t ktnplan = 0;                          // -ktnplan N with -ktamesgen: the walk is planned for a table of N entries (0: for -ktn)
+    bool range_given = false;                      // -pk or -pke stood on the command line
 };
 KangConfig parse_kangaroo_args(int argc, char **argv);
 

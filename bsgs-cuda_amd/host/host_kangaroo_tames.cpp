@@ -6,13 +6,19 @@
 //   bsgs_mi355x -kangaroo -ktamesgen FILE -ktn T -ktamesdev   the same herd, the growing table in device memory (include/bsgs_hip.h "Kangaroo, tame table grown
 //                                                 on the device"): each launch's records are inserted there (bsgs_kangaroo_run_tames_gen) and only merges, dead
 //                                                 kangaroos and cycles come back; GenRule is what they mean, without a device (-selftest kangaroo-tames-gen)
+//   ... -ktamesgen OUT -ktamesdev -ktamesfrom IN -ktn T   IN's entries are loaded into the growing table (bsgs_kangaroo_tames_gen_load) and a new herd walks with
+//                                                 IN's walk until T entries are there; -ktnplan N plans a table's walk for the size it is meant to reach
+//   bsgs_mi355x -kangaroo -ktamesmerge A,B -ktamesgen OUT   tables of one walk merged by tag on the host (tests/kangaroo_tames_extend_model.py restates both rules)
 // Neither writes kangaroo.work.  TamesRule is the search rule without a device: -selftest kangaroo-tames-search drives it with scripted records.
 // -ktamesgen -kwalk sym and -ktamessym FILE run the symmetric walk (include/bsgs_hip.h "Kangaroo, tame table for the symmetric walk"; tests/kangaroo_tames_sym_model.py): the
 // file is version 2 (R, the jump scale and R scalars), offsets are counted from the middle of the range and are those of representatives, the search's herd is
 // that of bsgs_kangaroo_setup_sym_keys and its records come back through bsgs_kangaroo_run_tames_keys, the entry numbers beside them.
 #include "host_kangaroo_list.h"
 
+#include <functional>
 #include <iostream>
+#include <queue>
+#include <random>
 
 namespace {
 using namespace kang;
@@ -218,6 +224,7 @@ public:
     enum What { RESEED, MERGE, HELD, DROPPED, IGNORED };
     explicit GenRule(uint64_t T) : T_(T) {}
     void entries(uint64_t n) { dev_ = n; }                            // entries in the device's table after a launch
+    void hold(uint64_t x, i128 d) { held_.emplace(x, d); }            // -ktamesfrom: the loaded table's entry with the tag the device cannot hold
     uint64_t total() const { return dev_ + held_.size(); }
     bool done() const { return total() >= T_; }
     // one record the device handed back, `reason` its reserved word (BSGS_KANGAROO_GEN_*): a dead kangaroo starts afresh; a duplicate has merged into a
@@ -247,19 +254,21 @@ private:
 
 // ---- -ktamesgen ---------------------------------------------------------------------------------------------------------------------------------------
 struct GenMode : Mode {
-    GenMode(const KangConfig &c, const Prologue &p) : c(c), T(c.ktn), rule(c.ktn)
+    GenMode(const KangConfig &c, const Prologue &p, TamesFile *from = nullptr) : c(c), T(c.ktn), Tplan(c.ktnplan ? c.ktnplan : c.ktn), from(from), rule(c.ktn)
     {
         saves = false;
         // dp: the command line's, else about (log2(W / T)) / 2 - 4: the trails stay a small part of the range while a wild walk to the next DP stays short
-        dp_fixed = c.dp >= 0 ? c.dp : (int)std::max(0.0, std::min(14.0, std::floor(std::log2((double)p.W / (double)T) / 2.0) - 4.0));
-        plan = tames_plan(p.W, T, (uint32_t)dp_fixed);                 // (-kwalk sym: planned() replaces it once the herd is known)
+        // (-ktnplan: T is the size the table is meant to reach; -ktamesfrom: the walk is the loaded table's, the plan only says where tame kangaroos start)
+        dp_fixed = from ? (int)from->dp : c.dp >= 0 ? c.dp : (int)std::max(0.0, std::min(14.0, std::floor(std::log2((double)p.W / (double)Tplan) / 2.0) - 4.0));
+        plan = tames_plan(p.W, Tplan, (uint32_t)dp_fixed);             // (-kwalk sym: planned() replaces it once the herd is known)
+        if (from) { plan.m = from->m; jump_scalars = from->js.data(); }
         mean_jump = (double)plan.m;
         expected = 2.0 * (double)T * std::ldexp(1.0, dp_fixed);
         herd_label = "herd (GPU, all tame), engine ";
         span = p.W + plan.E - 1;
         if (c.tames_sym) {                                             // -kwalk sym: R jump points, a launch longer than the cycle window
-            jumps = c.jumps ? c.jumps : 1024u;
-            jumpscale = c.jumpscale != 0.0 ? c.jumpscale : 1.0;
+            jumps = from ? from->R : c.jumps ? c.jumps : 1024u;
+            jumpscale = from ? from->jumpscale : c.jumpscale != 0.0 ? c.jumpscale : 1.0;
             min_launch = 2.0 * BSGS_KANGAROO_CYCLE_WINDOW;
         }
         if (!c.ktamesdev) map.reserve((size_t)T * 2);
@@ -268,8 +277,8 @@ struct GenMode : Mode {
     void planned(const Prologue &p) override
     {
         if (!c.tames_sym) return;
-        plan = tames_plan_sym(p.W, T, p.pl.dp, p.pl.kn * p.pl.engines);
-        mean_jump = std::max(1.0, std::min(std::ldexp(1.0, 62), jumpscale * (double)plan.m));
+        plan = tames_plan_sym(p.W, Tplan, p.pl.dp, p.pl.kn * p.pl.engines);
+        mean_jump = from ? (double)from->m : std::max(1.0, std::min(std::ldexp(1.0, 62), jumpscale * (double)plan.m));
         span = (p.W + 1) / 2 + plan.E - 1;
     }
     std::string fingerprint(const Prologue &, const WorkHeader &) const override { return ""; }
@@ -280,7 +289,25 @@ struct GenMode : Mode {
         if (c.tames_sym) { if (bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup_sym"; }
         else if (bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup";
         if (c.ktamesdev && bsgs_kangaroo_tames_gen_begin(dev, T) != BSGS_OK) return "bsgs_kangaroo_tames_gen_begin";
-        return nullptr;
+        return from ? load(dev) : nullptr;
+    }
+    // -ktamesfrom: the table begins with the capacity of the final table and takes the file's entries in, 24 bytes each; the one tag the device cannot hold
+    // (it can only be the first entry) is kept here, as a record with that tag is
+    const char *load(bsgs_dev *dev)
+    {
+        const auto ts = Clock::now();
+        const size_t skip = !from->x.empty() && from->x[0] == 0 ? 1 : 0;
+        uint64_t stored = 0, dup = 0, zero = 0, full = 0, n_entries = 0;
+        if (bsgs_kangaroo_tames_gen_load(dev, from->x.data() + skip, (const uint8_t *)(from->d.data() + skip), from->x.size() - skip, &stored, &dup, &zero, &full, &n_entries) != BSGS_OK)
+            return "bsgs_kangaroo_tames_gen_load";
+        if (skip) rule.hold(0, from->d[0]);
+        rule.entries(n_entries);
+        loaded = stored + skip;
+        printf("Loaded %llu entries of the table into GPU memory, %llu duplicates%s, %.3fs\n", (unsigned long long)loaded, (unsigned long long)dup,
+               full || zero ? " (entries were lost: the file is not a sound table)" : "", since(ts));
+        std::vector<uint64_t>().swap(from->x);
+        std::vector<i128>().swap(from->d);
+        return full || zero ? "bsgs_kangaroo_tames_gen_load (the table did not take every entry)" : nullptr;
     }
     // every kangaroo is tame: t uniform in [1, W + E), with -kwalk sym in [1, ceil(W/2) + E), d = t
     const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) override
@@ -307,42 +334,40 @@ struct GenMode : Mode {
         if (rule.done()) sh.stop = true;
         return rc;
     }
-    // -ktamesdev, in the engine's thread before its device is closed: the finished table leaves the device, takes the host's entries in, is sorted and cut
-    // to the T lowest tags, and every entry that will be written is checked against d*G on this engine
+    // -ktamesdev, in the engine's thread before its device is closed: the finished table leaves the device sorted and cut to the T lowest tags
+    // (bsgs_kangaroo_tames_gen_read_sorted), the host's entries go in front, and every entry that will be written is checked against d*G on this engine
     std::string ending(bsgs_dev *dev, uint32_t, Shared &sh) override
     {
         if (!c.ktamesdev) return "";
         std::lock_guard<std::mutex> lt(sh.tab_m);
         if (!rule.done()) return "";
         walked = since(pro->t0);
-        uint64_t n = 0;
-        (void)bsgs_kangaroo_tames_gen_read(dev, nullptr, nullptr, 0, &n);      // the count alone
-        std::vector<uint64_t> x((size_t)n);
-        std::vector<i128> d((size_t)n);
-        if (n && bsgs_kangaroo_tames_gen_read(dev, x.data(), (uint8_t *)d.data(), n, &n) != BSGS_OK) return std::string("bsgs_kangaroo_tames_gen_read: ") + bsgs_last_error();
-        table.reserve((size_t)n + rule.held().size());
-        for (uint64_t i = 0; i < n; i++) table.emplace_back(x[i], d[i]);
-        std::vector<uint64_t>().swap(x);
-        std::vector<i128>().swap(d);
-        for (const auto &kv : rule.held()) table.push_back(kv);
-        if (table.size() < T) return "growing tame table: " + std::to_string(table.size()) + " entries read, " + std::to_string(T) + " counted";
-        std::sort(table.begin(), table.end());
-        table.resize((size_t)T);
+        // the device sorts and cuts: the host's entries have the tag 0 and sort first, so the T - (held) lowest tags of the device complete the table
+        const auto tr = Clock::now();
+        const uint64_t held = std::min<uint64_t>(T, rule.held().size()), want = T - held;
+        uint64_t n = 0, h = 0;
+        tx.resize((size_t)T); td.resize((size_t)T);                    // the file's two columns, filled in place
+        for (const auto &kv : rule.held()) if (h < held) { tx[h] = kv.first; td[h] = kv.second; h++; }
+        const int rc = bsgs_kangaroo_tames_gen_read_sorted(dev, tx.data() + held, (uint8_t *)(td.data() + held), want, &n);
+        if (rc != BSGS_OK || n < want) {
+            tx.clear(); td.clear();
+            return rc != BSGS_OK ? std::string("bsgs_kangaroo_tames_gen_read_sorted: ") + bsgs_last_error() :
+                                   "growing tame table: " + std::to_string(n + held) + " entries read, " + std::to_string(T) + " counted";
+        }
         (void)bsgs_kangaroo_tames_gen_end(dev);
+        read_secs = since(tr);
         if (!c.verify) return "";
         const auto ts = Clock::now();
         uint8_t g[64];
         hs::affine_to_le(hs::G, g, g + 32);
         const uint64_t step = 1u << 20;
         std::vector<uint32_t> fl((size_t)std::min(T, step), 0u);
-        x.resize(fl.size()); d.resize(fl.size());
         for (uint64_t pos = 0; pos < T; pos += step) {
             const uint32_t m = (uint32_t)std::min(T - pos, step);
-            for (uint32_t k = 0; k < m; k++) { x[k] = table[pos + k].first; d[k] = table[pos + k].second; }
             uint32_t n_bad = 0, first = 0;
-            if (bsgs_kangaroo_verify_points(dev, g, m, (const uint8_t *)d.data(), fl.data(), x.data(), &n_bad, &first, 1) != BSGS_OK)
+            if (bsgs_kangaroo_verify_points(dev, g, m, (const uint8_t *)&td[pos], fl.data(), &tx[pos], &n_bad, &first, 1) != BSGS_OK)
                 return std::string("bsgs_kangaroo_verify_points: ") + bsgs_last_error();
-            if (n_bad) { table.clear(); return "Tame table is damaged: entry " + std::to_string(pos + first) + " does not match its offset"; }
+            if (n_bad) { tx.clear(); td.clear(); return "Tame table is damaged: entry " + std::to_string(pos + first) + " does not match its offset"; }
         }
         printf("\n[verify] tame table: %llu entries %.3fs\n", (unsigned long long)T, since(ts));
         return "";
@@ -389,7 +414,9 @@ struct GenMode : Mode {
     const WorkKeys *save(WorkHeader &, std::vector<uint8_t> &) override { return nullptr; }
 
     const KangConfig &c;
-    const uint64_t T;
+    const uint64_t T, Tplan;                                           // the entries to make; the entries the walk is planned for (-ktnplan)
+    TamesFile *const from;                                             // -ktamesfrom: the table that is extended (its entries until they are loaded)
+    uint64_t loaded = 0;
     const Prologue *pro = nullptr;
     TamesPlan plan;
     u128 span;
@@ -400,17 +427,51 @@ struct GenMode : Mode {
     GenRule rule;
     std::atomic<uint64_t> seen{0};
     uint64_t handed_back = 0;
-    std::vector<std::pair<uint64_t, i128>> table;
-    double walked = 0.0;                                               // seconds from the start to the launch that completed the table
+    std::vector<uint64_t> tx;
+    std::vector<i128> td;
+    double walked = 0.0, read_secs = 0.0;                              // seconds from the start to the launch that completed the table; of the sorted read
 };
 
-int tames_generate(const KangConfig &c)
+void tames_verify(const TamesFile &f, int gpu);
+
+std::string find_tames(const KangConfig &c, std::string path)
 {
+    struct stat sb;
+    if (stat(path.c_str(), &sb) != 0 && stat((c.dir + "/" + path).c_str(), &sb) == 0) path = c.dir + "/" + path;
+    return path;
+}
+
+int tames_generate(const KangConfig &c_in)
+{
+    KangConfig c = c_in;
+    // -ktamesfrom: the table is read and every refusal is made before any device is looked for; the walk is the file's, and what the command line names of it
+    // must be what the file says
+    TamesFile in;
+    const bool extend = !c.ktamesfrom.empty();
+    if (extend) {
+        const std::string bad = read_tames(find_tames(c, c.ktamesfrom), in, c.tames_sym ? TAMES_VERSION_SYM : TAMES_VERSION);
+        if (!bad.empty()) die("-ktamesfrom: " + bad);
+        if (c.ktn <= in.x.size()) die("-ktamesfrom: -ktn " + std::to_string(c.ktn) + " must be above the " + std::to_string(in.x.size()) + " entries of the table that is extended");
+        if (c.seed_given && c.seed == in.seed) die("-ktamesfrom: -kseed is the seed the table was made with (the new herd would retrace its starts): give another");
+        if (c.dp >= 0 && (uint32_t)c.dp != in.dp) die("-ktamesfrom: -dp " + std::to_string(c.dp) + " differs from the table's -dp " + std::to_string(in.dp));
+        if (c.jumps && c.jumps != in.R) die("-ktamesfrom: -kjumps " + std::to_string(c.jumps) + " differs from the table's " + std::to_string(in.R));
+        if (c.jumpscale != 0.0 && c.jumpscale != in.jumpscale) die("-ktamesfrom: -kjumpscale differs from the table's");
+        if (!c.range_given) { c.pk = hs::fe_to_hex(in.lo); c.pke = hs::fe_to_hex(in.hi); }
+    }
     Prologue p(c);
+    if (extend && (hs::fe_cmp(p.lo, in.lo) != 0 || hs::fe_cmp(p.hi, in.hi) != 0)) die("-ktamesfrom: Tame table was made for another range");
+    if (extend && !c.seed_given) {                                     // no -kseed: drawn here, so that it is not the file's by chance
+        std::random_device rd;
+        do c.seed = ((uint64_t)rd() << 32) ^ rd(); while (c.seed == in.seed);
+        c.seed_given = true;
+    }
     printf("Kangaroo range [%s, %s], width 2^%.2f: a tame table of %llu entries\n", hs::fe_to_hex(p.lo).c_str(), hs::fe_to_hex(p.hi).c_str(), std::log2((double)p.W),
            (unsigned long long)c.ktn);
-    GenMode mode(c, p);
+    if (extend) printf("Extending a table of %zu entries made with %.3e steps: its walk is taken over\n", in.x.size(), (double)in.steps);
+    const uint64_t in_steps = in.steps, in_T = in.x.size();
+    GenMode mode(c, p, extend ? &in : nullptr);
     p.complete(c, mode);
+    if (extend && c.verify) tames_verify(in, p.gpus[0]);
     if (c.tames_sym) printf("Plan: symmetric walk, %u jump points, jump scale %g, mean jump m = %llu, tame starts reach E = 0x%s past the half range, -dp %u\n", mode.jumps, mode.jumpscale,
                             (unsigned long long)mode.mean_jump, u128_hex(mode.plan.E).c_str(), p.pl.dp);
     else printf("Plan: mean jump m = %llu, tame starts reach E = 0x%s past the range, -dp %u\n", (unsigned long long)mode.plan.m, u128_hex(mode.plan.E).c_str(), p.pl.dp);
@@ -423,17 +484,16 @@ int tames_generate(const KangConfig &c)
         return o == GAVE_UP ? 1 : 3;
     }
     TamesFile f;
-    f.dp = p.pl.dp; f.lo = p.lo; f.hi = p.hi; f.steps = sh.steps.load(); f.seed = p.wh.seed; f.m = mode.plan.m; f.js = p.js;
-    if (c.tames_sym) { f.version = TAMES_VERSION_SYM; f.R = mode.jumps; f.jumpscale = mode.jumpscale; f.m = (uint64_t)mode.mean_jump; }
-    std::vector<std::pair<uint64_t, i128>> en;
-    if (c.ktamesdev) en.swap(mode.table);                              // read, completed, sorted, cut and verified in the engine's thread (GenMode::ending)
+    f.dp = p.pl.dp; f.lo = p.lo; f.hi = p.hi; f.steps = in_steps + sh.steps.load(); f.seed = p.wh.seed; f.m = mode.plan.m; f.js = p.js;
+    if (c.tames_sym) { f.version = TAMES_VERSION_SYM; f.R = mode.jumps; f.jumpscale = mode.jumpscale; f.m = extend ? in.m : (uint64_t)mode.mean_jump; }
+    if (c.ktamesdev) { f.x.swap(mode.tx); f.d.swap(mode.td); }         // read sorted and cut, completed and verified in the engine's thread (GenMode::ending)
     else {
-        en.assign(mode.map.begin(), mode.map.end());
+        std::vector<std::pair<uint64_t, i128>> en(mode.map.begin(), mode.map.end());
         std::sort(en.begin(), en.end());
         en.resize((size_t)c.ktn);
+        for (const auto &kv : en) { f.x.push_back(kv.first); f.d.push_back(kv.second); }
     }
-    if (en.size() != c.ktn) die("tame table: " + std::to_string(en.size()) + " entries of " + std::to_string(c.ktn));
-    for (const auto &kv : en) { f.x.push_back(kv.first); f.d.push_back(kv.second); }
+    if (f.x.size() != c.ktn || f.d.size() != c.ktn) die("tame table: " + std::to_string(f.x.size()) + " entries of " + std::to_string(c.ktn));
     std::string path = c.ktamesgen;
     if (path.find('/') == std::string::npos) path = c.dir + "/" + path;
     if (!write_tames(path, f)) die("cannot write " + path);
@@ -441,6 +501,9 @@ int tames_generate(const KangConfig &c)
            (unsigned long long)(c.ktamesdev ? mode.seen.load() : sh.dps.load()), (unsigned long long)mode.n_merges(), secs);
     if (c.ktamesdev) printf("Table grown on the GPU: %llu records inserted there, %llu handed back over the bus (%llu dropped), %.2fs of walking\n", (unsigned long long)mode.seen.load(),
                             (unsigned long long)mode.handed_back, (unsigned long long)sh.dropped.load(), mode.walked);
+    if (c.ktamesdev) printf("Table sorted and cut on the GPU: %.3fs for the sorted read, %.2fs from the last launch to the file\n", mode.read_secs, since(p.t0) - mode.walked);
+    if (extend) printf("Extended from %llu to %llu entries: %llu loaded, %.3e steps of this run, %.3e in all\n", (unsigned long long)in_T, (unsigned long long)c.ktn,
+                       (unsigned long long)mode.loaded, (double)sh.steps.load(), (double)f.steps);
     fflush(stdout);
     return 0;
 }
@@ -690,9 +753,74 @@ int tames_search(const KangConfig &c)
     fflush(stdout);
     return o == DONE ? 0 : (o == BUDGET || o == INTERRUPTED) ? 3 : 1;
 }
+// ---- -ktamesmerge ---------------------------------------------------------------------------------------------------------------------------------------
+// "" when b was made by the walk of a, else the first field that differs, in the header's order
+std::string walk_differs(const TamesFile &a, const TamesFile &b)
+{
+    if (a.dp != b.dp) return "-dp " + std::to_string(b.dp) + " against " + std::to_string(a.dp);
+    if (hs::fe_cmp(a.lo, b.lo) != 0 || hs::fe_cmp(a.hi, b.hi) != 0) return "the range [" + hs::fe_to_hex(b.lo) + ", " + hs::fe_to_hex(b.hi) + "] is another";
+    if (a.m != b.m) return "mean jump " + std::to_string(b.m) + " against " + std::to_string(a.m);
+    if (a.R != b.R) return "-kjumps " + std::to_string(b.R) + " against " + std::to_string(a.R);
+    if (memcmp(&a.jumpscale, &b.jumpscale, 8) != 0) return "the jump scale differs";
+    for (uint32_t j = 0; j < a.R; j++) if (a.js[j] != b.js[j]) return "jump scalar " + std::to_string(j) + " differs";
+    return "";
+}
+
+// a k-way merge by tag of tables that are strictly ascending each: one entry per tag, the first table that has it wins; the T lowest tags are written
+int tames_merge(const KangConfig &c)
+{
+    std::vector<std::string> paths;
+    for (const std::string &s : split_commas(c.ktamesmerge)) if (!s.empty()) paths.push_back(find_tames(c, s));
+    if (paths.size() < 2) die("-ktamesmerge needs at least two tables: A,B[,C...]");
+    std::vector<TamesFile> in(paths.size());
+    for (size_t i = 0; i < paths.size(); i++) {
+        const std::string bad = read_tames(paths[i], in[i], c.tames_sym ? TAMES_VERSION_SYM : TAMES_VERSION);
+        if (!bad.empty()) die("-ktamesmerge: " + bad);
+        const std::string differs = i ? walk_differs(in[0], in[i]) : "";
+        if (!differs.empty()) die("-ktamesmerge: " + paths[i] + " was not made by the walk of " + paths[0] + ": " + differs);
+    }
+    TamesFile f;
+    f.version = in[0].version; f.dp = in[0].dp; f.lo = in[0].lo; f.hi = in[0].hi; f.seed = in[0].seed; f.m = in[0].m; f.R = in[0].R; f.jumpscale = in[0].jumpscale; f.js = in[0].js;
+    uint64_t total = 0, dropped = 0;
+    for (const TamesFile &t : in) { f.steps += t.steps; total += t.x.size(); }
+    typedef std::pair<uint64_t, size_t> Head;                          // (tag, table): the lowest tag first, of equal tags the earlier table
+    std::priority_queue<Head, std::vector<Head>, std::greater<Head>> heads;
+    std::vector<size_t> at(in.size(), 0);
+    for (size_t i = 0; i < in.size(); i++) heads.push(Head(in[i].x[0], i));
+    const uint64_t keep = c.ktn ? c.ktn : ~0ull;
+    uint64_t tags = 0, last = 0;
+    while (!heads.empty()) {
+        const Head h = heads.top();
+        heads.pop();
+        const size_t i = h.second;
+        if (tags && h.first == last) dropped++;                        // an earlier table had the tag
+        else {
+            tags++;
+            last = h.first;
+            if (f.x.size() < keep) { f.x.push_back(h.first); f.d.push_back(in[i].d[at[i]]); }
+        }
+        if (++at[i] < in[i].x.size()) heads.push(Head(in[i].x[at[i]], i));
+    }
+    printf("Merged %zu tame tables: %llu entries in all, %llu distinct tags, %llu dropped because an earlier table had their tag\n", in.size(), (unsigned long long)total,
+           (unsigned long long)tags, (unsigned long long)dropped);
+    if (c.ktn > tags) die("-ktamesmerge: -ktn " + std::to_string(c.ktn) + " is above the " + std::to_string(tags) + " tags of the union; nothing written");
+    if (tags > (1ull << 31) && !c.ktn) die("-ktamesmerge: the union has " + std::to_string(tags) + " tags, a table holds at most 2^31: cut it with -ktn");
+    if (c.verify) {                                                    // every entry written, on the first -d device; -noverify opens no device at all
+        int ngpu = 0;
+        CK(bsgs_dev_count(&ngpu));
+        if (ngpu <= 0) die("No GPU found");
+        tames_verify(f, c.devices.empty() ? 0 : atoi(c.devices.c_str()));
+    }
+    std::string path = c.ktamesgen;
+    if (path.find('/') == std::string::npos) path = c.dir + "/" + path;
+    if (!write_tames(path, f)) die("cannot write " + path);
+    printf("Tame table %s: %zu entries, %.3e steps\n", path.c_str(), f.x.size(), (double)f.steps);
+    fflush(stdout);
+    return 0;
+}
 }  // namespace
 
-int kangaroo_tames_main(const KangConfig &c) { return c.ktamesgen.empty() ? tames_search(c) : tames_generate(c); }
+int kangaroo_tames_main(const KangConfig &c) { return !c.ktamesmerge.empty() ? tames_merge(c) : c.ktamesgen.empty() ? tames_search(c) : tames_generate(c); }
 
 // -selftest kangaroo-tames [sym] FILE [pk pke]: the header fields of a tame table, its ordering, and with a range whether it is the table's.  sym: the reader
 // of -ktamessym (version 2; two more lines, "jumps <R>" and "jump scale <s>"), else the reader of -ktames (version 1)

@@ -31,6 +31,7 @@ NATIVE_SYMBOLS = [
     "bsgs_kangaroo_set_keys", "bsgs_kangaroo_seed_keys", "bsgs_kangaroo_verify", "bsgs_kangaroo_verify_points", "bsgs_selftest_fe3",
     "bsgs_kangaroo_tames_image", "bsgs_kangaroo_tames_install", "bsgs_kangaroo_run_tames", "bsgs_kangaroo_tames_install_keys", "bsgs_kangaroo_run_tames_keys",
     "bsgs_kangaroo_tames_gen_begin", "bsgs_kangaroo_run_tames_gen", "bsgs_kangaroo_tames_gen_insert", "bsgs_kangaroo_tames_gen_read", "bsgs_kangaroo_tames_gen_end",
+    "bsgs_kangaroo_tames_gen_load", "bsgs_kangaroo_tames_gen_read_sorted",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
@@ -203,6 +204,8 @@ def lib():
             "bsgs_kangaroo_tames_gen_insert": [vp, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
             "bsgs_kangaroo_tames_gen_read": [vp, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64)],
             "bsgs_kangaroo_tames_gen_end": [vp],
+            "bsgs_kangaroo_tames_gen_load": [vp, vp, vp, C.c_uint64] + [C.POINTER(C.c_uint64)] * 5,
+            "bsgs_kangaroo_tames_gen_read_sorted": [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)],
             "bsgs_kangaroo_run_tames_keys": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_float)],
         }
@@ -820,6 +823,31 @@ class Device:
 
     def kangaroo_tames_gen_end(self):
         _chk(self.L.bsgs_kangaroo_tames_gen_end(self.h))
+
+    def kangaroo_tames_gen_load(self, tags, d):
+        """n (tag, d) pairs into the growing table, 24 bytes each: tags = n integers or the bytes of n little-endian u64, d = n integers (taken mod 2^128) or
+        the bytes of n 16-byte offsets -> (stored, duplicate, zero, full, n_entries)"""
+        tb = bytes(tags) if isinstance(tags, (bytes, bytearray, memoryview)) else b"".join(t.to_bytes(8, "little") for t in tags)
+        db = bytes(d) if isinstance(d, (bytes, bytearray, memoryview)) else b"".join((v % (1 << 128)).to_bytes(16, "little") for v in d)
+        n = len(tb) // 8
+        assert len(tb) == 8 * n and len(db) == 16 * n
+        out = [C.c_uint64() for _ in range(5)]
+        _chk(self.L.bsgs_kangaroo_tames_gen_load(self.h, C.c_char_p(tb), C.c_char_p(db), n, *[C.byref(v) for v in out]))
+        return tuple(v.value for v in out)
+
+    def kangaroo_tames_gen_read_sorted(self, max_entries=None, raw=False):
+        """the table's entries ascending by tag, sorted on the device, cut to the max_entries lowest tags (None: all of them): (list of (tag, d mod 2^128), the
+        table's entry count); raw: the tags and the offsets as bytes in the place of the list"""
+        n = C.c_uint64()
+        _chk(self.L.bsgs_kangaroo_tames_gen_read_sorted(self.h, None, None, 0, C.byref(n)))
+        m = n.value if max_entries is None else max_entries
+        tags, d = C.create_string_buffer(8 * max(1, m)), C.create_string_buffer(16 * max(1, m))
+        _chk(self.L.bsgs_kangaroo_tames_gen_read_sorted(self.h, tags, d, m, C.byref(n)))
+        got = min(m, n.value)
+        tb, db = tags.raw[:8 * got], d.raw[:16 * got]
+        if raw:
+            return (tb, db), n.value
+        return [(int.from_bytes(tb[8 * k:8 * k + 8], "little"), int.from_bytes(db[16 * k:16 * k + 16], "little")) for k in range(got)], n.value
 
     def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):
         """start points on the GPU: kangaroo idx[k] (first + k without idx) := (d*G or Q + d*G, d, flags[k]) for d = offsets[k] (a signed integer) and

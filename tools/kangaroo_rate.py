@@ -3,6 +3,7 @@
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
     tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--no-vgprs] [--out FILE]
+    tools/kangaroo_rate.py --tamesload N | --tamessort N [--reps 3] [--out FILE]
 
 --sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch); with --keys
 the herd of bsgs_kangaroo_setup_sym_keys, whose kernel entry point reads a kangaroo's key when it writes a record (keys 0..15 dealt out over the herd).
@@ -14,6 +15,10 @@ With --sym --keys the table is that of the keyed herd (bsgs_kangaroo_tames_insta
 --tamesgen N begins a growing tame table of capacity N (bsgs_kangaroo_tames_gen_begin) under an all-tame herd of pairwise different starts (seeded on the
 GPU: repeated starts would make every record a duplicate) and times bsgs_kangaroo_run_tames_gen and bsgs_kangaroo_run in turn, launch by launch, in one
 process: the difference of their kernel times is the insert.  Plain walk, or with --sym the symmetric one (the generators of -ktamesgen -ktamesdev).
+
+--tamesload N times bsgs_kangaroo_tames_gen_load of N synthetic entries (pairwise different tags, 24 bytes each from pageable host memory) into a fresh growing
+table of capacity N, --reps times.  --tamessort N loads such a table once and times bsgs_kangaroo_tames_gen_read_sorted of all N entries (harvest, radix sort,
+gather and the copy to the host) against bsgs_kangaroo_tames_gen_read (harvest and copy, unsorted), in turn.  Both run under the smallest herd; no walk.
 
 The starts are 65536 distinct points P0 + i*G, repeated over the herd (the walk's cost does not depend on which point a kangaroo stands on; repeats only
 make their DPs coincide)."""
@@ -49,6 +54,65 @@ def vgprs(sym=False, keys=False):
         return None
 
 
+def table_legs(a):
+    """--tamesload / --tamessort: the load into and the sorted read of a growing tame table, without a walk"""
+    import numpy as np
+    n = a.tamesload or a.tamessort
+    dev = pybsgs.Device(0)
+    L = dev.L
+    scal = [(0x9E3779B97F4A7C15 * (j + 1)) % (1 << 62) + 1 for j in range(64)]
+    dev.kangaroo_setup([mul(s) for s in scal], scal, 16, 64, 1, 64)
+    tags = np.arange(1, n + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)      # an odd multiplier: pairwise different, none zero
+    d = np.empty((n, 2), dtype=np.uint64)
+    d[:, 0] = tags ^ np.uint64(0x5555555555555555)
+    d[:, 1] = np.arange(n, dtype=np.uint64)
+    counts = [C.c_uint64() for _ in range(5)]
+    u64p = C.POINTER(C.c_uint64)
+
+    def load():
+        t0 = time.perf_counter()
+        pybsgs._chk(L.bsgs_kangaroo_tames_gen_load(dev.h, tags.ctypes.data, d.ctypes.data, n, *[C.byref(c) for c in counts]))
+        s = time.perf_counter() - t0
+        assert [c.value for c in counts] == [n, 0, 0, 0, n], [c.value for c in counts]
+        return s
+
+    res = {"gpu": dev.name(), "entries": n, "slots": 1 << max(7, (2 * (n + 64) - 1).bit_length()), "bytes_per_entry": 24}
+    if a.tamesload:
+        begin, secs = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            pybsgs._chk(L.bsgs_kangaroo_tames_gen_begin(dev.h, n))
+            begin.append(time.perf_counter() - t0)
+            secs.append(load())
+        res.update({"what": "load of synthetic entries into a growing tame table (bsgs_kangaroo_tames_gen_load), pageable host memory", "begin_s_each": begin, "load_s_each": secs,
+                    "load_s": min(secs), "entries_per_s": n / min(secs), "host_GBps": 24 * n / min(secs) / 1e9})
+    else:
+        pybsgs._chk(L.bsgs_kangaroo_tames_gen_begin(dev.h, n))
+        load()
+        xs, ds, cnt = np.empty(n, dtype=np.uint64), np.empty((n, 2), dtype=np.uint64), C.c_uint64()
+        srt, plain = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            pybsgs._chk(L.bsgs_kangaroo_tames_gen_read(dev.h, xs.ctypes.data_as(u64p), ds.ctypes.data, n, C.byref(cnt)))
+            plain.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            pybsgs._chk(L.bsgs_kangaroo_tames_gen_read_sorted(dev.h, xs.ctypes.data, ds.ctypes.data, n, C.byref(cnt)))
+            srt.append(time.perf_counter() - t0)
+        assert cnt.value == n and bool(np.all(xs[1:] > xs[:-1])) and bool(np.all(ds[:, 0] == xs ^ np.uint64(0x5555555555555555)))
+        t0 = time.perf_counter()
+        np.argsort(xs[::-1].copy(), kind="stable")                    # one host thread sorting the tags alone, for scale
+        host_sort = time.perf_counter() - t0
+        res.update({"what": "sorted read of a growing tame table (bsgs_kangaroo_tames_gen_read_sorted: harvest, radix sort on the device, gather, copy) against the unsorted read",
+                    "read_sorted_s_each": srt, "read_unsorted_s_each": plain, "read_sorted_s": min(srt), "read_unsorted_s": min(plain), "sort_on_device_s": min(srt) - min(plain),
+                    "entries_per_s": n / min(srt), "numpy_argsort_of_the_tags_s": host_sort, "checked": "ascending, each d with its tag"})
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    dev.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=256)
@@ -61,6 +125,9 @@ def main():
     ap.add_argument("--keys", action="store_true")
     ap.add_argument("--tames", type=int, default=0)
     ap.add_argument("--tamesgen", type=int, default=0)
+    ap.add_argument("--tamesload", type=int, default=0)
+    ap.add_argument("--tamessort", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-vgprs", action="store_true", help="do not compile the walk's unit for its VGPR count")
     ap.add_argument("--out")
     a = ap.parse_args()
@@ -68,6 +135,8 @@ def main():
         ap.error("--keys goes with --sym")
     if a.tamesgen and (a.keys or a.tames):
         ap.error("--tamesgen goes with the plain walk or --sym alone")
+    if a.tamesload or a.tamessort:
+        return table_legs(a)
     dev = pybsgs.Device(0)
     L = dev.L
     cus = C.c_int()
