@@ -18,7 +18,8 @@ int bsgs_fail(int code, const char *fmt, ...);
 
 // kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table, the staging of a seed call and the key list;
 // kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records;
-// kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer; kangaroo_tames_extend.hip: its load and sorted read
+// kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer; kangaroo_tames_extend.hip: its load and sorted read;
+// kangaroo_dptable.hip: the distinguished-point table of a search with its own buffer of hand-backs
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
     u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
@@ -44,6 +45,12 @@ struct bsgs_kangaroo {
     u32x4 *gen_d = nullptr;                // ... and the offset of each
     u64 *gen_ctr = nullptr;                // eight words: entries in the table, occupied slots met by the last harvest; kangaroo_tames_extend.hip: the four counts of a load, OR and AND of the tags
     uint64_t gen_slots = 0;
+    u64 *dpt_tag = nullptr;                // bsgs_kangaroo_dptable_begin (kangaroo_dptable.hip): dpt_slots tags (a power of two; 0 = empty) ...
+    u32x4 *dpt_d = nullptr;                // ... the offset of each ...
+    u32 *dpt_who = nullptr;                // ... and its owner: kangaroo, type (two words per slot)
+    u32 *dpt_out = nullptr;                // the hand-backs of a launch: u64 places taken, u64 records handed back | 2 * cap records from byte 64
+    u64 *dpt_ctr = nullptr;                // eight words: entries in the table, occupied slots met by the last harvest, the four counts of a load
+    uint64_t dpt_slots = 0;
 };
 
 struct bsgs_dev {

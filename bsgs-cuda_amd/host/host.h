@@ -232,6 +232,8 @@ int kangaroo_main(int argc, char **argv);
 int kangaroo_selftest(const std::vector<std::string> &args);
 int kangaroo_work_selftest(const std::vector<std::string> &args);
 int kangaroo_roundtrip_selftest(const std::vector<std::string> &args);
+int kangaroo_dpdev_selftest(const std::vector<std::string> &args);               // -selftest kangaroo-dpdev [sym]: the hand-back rule of -kdpdev on scripted records and pairs
+int kangaroo_dpdev_plan_selftest(const std::vector<std::string> &args);          // -selftest kangaroo-dpdev-plan: the plan of -kdpdev (dp, herd, launch, record buffer, capacity)
 int kangaroo_sym_selftest(const std::vector<std::string> &args);                 // -selftest kangaroo-sym: the symmetric walk's table
 int kangaroo_sym_roundtrip_selftest(const std::vector<std::string> &args);       // -selftest kangaroo-sym-roundtrip: through a version-2 work file
 int kangaroo_multi_roundtrip_selftest(const std::vector<std::string> &args);     // -selftest kangaroo-multi-roundtrip: through a version-3 work file

@@ -6,6 +6,9 @@
 // it through a work file.
 // -ksym runs the symmetric walk (the negation map; include/bsgs_hip.h "Kangaroo, symmetric walk"): offsets counted from the middle of the range, R jump points
 // (-kjumps) of mean -kjumpscale * N_k sqrt(W) / 4, the collision rule with signs, cycles counted, a version-2 work file; -selftest kangaroo-sym / kangaroo-sym-roundtrip.
+// -kdpdev keeps the distinguished points in device memory (include/bsgs_hip.h "Kangaroo, distinguished-point table in device memory"): the launch inserts and
+// pairs them there, the collector judges the handed-back pairs by the table's own rule, the device table is read where the herd is downloaded for a save and
+// loaded at -wl; the plan is a low dp and the full herd; -selftest kangaroo-dpdev / kangaroo-dpdev-plan.
 #include "host_kangaroo_run.h"
 
 #include <unordered_map>
@@ -38,6 +41,7 @@ bool parse_hex128(const std::string &s, u128 &v)
 
 // ---- the table of distinguished points: keyed on the low 64 bits of x, shared by all engines ---------------------------------------------------------
 class KangarooTable {
+    struct Entry { u128 d; uint32_t kid; bool wild, neg; };
 public:
     enum Verdict { NEW, FOUND, RESEED, FALSE_MATCH, REPEAT };
     // sym: the rule of the symmetric walk (include/bsgs_hip.h "Kangaroo, symmetric walk"; tests/kangaroo_sym_model.py SymTable)
@@ -54,11 +58,22 @@ public:
         if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; if (flags & BSGS_KANGAROO_CYCLE) cycles_++; return RESEED; }
         uint64_t k64;
         memcpy(&k64, x, 8);
-        if (sym_) return add_sym(k64, d, kid, flags, key);
         const bool wild = flags & BSGS_KANGAROO_WILD;
-        auto it = map_.find(k64);
-        if (it == map_.end()) { map_.emplace(k64, Entry{d, kid, wild, false}); return NEW; }
-        const Entry &e = it->second;
+        auto it = map_.find(k64);                                      // look the tag up ...
+        if (it == map_.end()) { map_.emplace(k64, Entry{d, kid, wild, sym_ && wild && (flags & BSGS_KANGAROO_NEG)}); return NEW; }
+        return judge(it->second, d, kid, flags, key);                  // ... and judge the record against that entry
+    }
+    // -kdpdev: a record the device table handed back as a duplicate, against the stored entry it came with (d, kangaroo, type: 0 tame, 1 wild, 3 wild with
+    // NEG); the host's map is not touched.  The verdicts of add() for the same pair, never NEW
+    Verdict add_pair(u128 ed, uint32_t ekid, uint32_t etype, u128 d, uint32_t kid, uint32_t flags, Scalar *key)
+    {
+        if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; if (flags & BSGS_KANGAROO_CYCLE) cycles_++; return RESEED; }
+        return judge(Entry{ed, ekid, (etype & 1u) != 0, sym_ && etype == 3u}, d, kid, flags, key);
+    }
+    Verdict judge(const Entry &e, u128 d, uint32_t kid, uint32_t flags, Scalar *key)
+    {
+        if (sym_) return judge_sym(e, d, kid, flags, key);
+        const bool wild = flags & BSGS_KANGAROO_WILD;
         if (e.wild == wild) {
             if (e.kid == kid) return REPEAT;
             reseeds_++;
@@ -102,15 +117,11 @@ public:
         return true;
     }
 private:
-    struct Entry { u128 d; uint32_t kid; bool wild, neg; };
     // a record's point is sigma Q + d G, sigma = 0 tame, +1 wild, -1 wild with NEG; equal x: sigma1 Q + d1 G = +-(sigma2 Q + d2 G), so for each sign with
     // sigma1 -+ sigma2 != 0 the candidate is k'' = (+-d2 - d1) / (sigma1 -+ sigma2) mod n (the divisor is +-1 or +-2), the key a + W/2 + k''
-    Verdict add_sym(uint64_t k64, u128 d, uint32_t kid, uint32_t flags, Scalar *key)
+    Verdict judge_sym(const Entry &e, u128 d, uint32_t kid, uint32_t flags, Scalar *key)
     {
         const bool wild = flags & BSGS_KANGAROO_WILD, neg = wild && (flags & BSGS_KANGAROO_NEG);
-        auto it = map_.find(k64);
-        if (it == map_.end()) { map_.emplace(k64, Entry{d, kid, wild, neg}); return NEW; }
-        const Entry &e = it->second;
         if (e.kid == kid) return REPEAT;
         const int s1 = e.wild ? (e.neg ? -1 : 1) : 0, s2 = wild ? (neg ? -1 : 1) : 0;
         const Scalar d1 = sc_from_i128((i128)e.d), d2 = sc_from_i128((i128)d);
@@ -198,6 +209,61 @@ int kangaroo_sym_selftest(const std::vector<std::string> &a)
     return 0;
 }
 
+// -selftest kangaroo-dpdev [sym] <pk hex> <pke hex> <pubkey> <item>...: the hand-back rule of -kdpdev without a GPU.  An item is a scripted record as
+// -selftest kangaroo (sym: kangaroo-sym) takes it -- what the device hands back alone: DEAD, tag 0, a full table -- and goes through the host's own map; or
+// S,<tag hex>,<d hex>,<kangaroo>,<type> followed by its record: a duplicate, judged against the stored entry it came with.  The same verdict and summary lines.
+int kangaroo_dpdev_selftest(const std::vector<std::string> &args)
+{
+    std::vector<std::string> a(args);
+    const bool sym = !a.empty() && a[0] == "sym";
+    if (sym) a.erase(a.begin());
+    if (a.size() < 3) return 2;
+    Scalar lo, hi; Affine P; u128 W;
+    if (!parse_range_pub(a[0], a[1], a[2], lo, hi, P, W)) return 2;
+    KangarooTable tab(lo, W, P, sym);
+    for (size_t i = 3; i < a.size(); i++) {
+        if (a[i].compare(0, 2, "S,") != 0) { if (!scripted_record(tab, a[i], sym)) return 2; continue; }
+        const std::vector<std::string> s = split_commas(a[i]);
+        if (s.size() != 5 || i + 1 >= a.size()) return 2;
+        const std::vector<std::string> f = split_commas(a[++i]);
+        u128 tag, ed, d;
+        Scalar x;
+        if (f.size() != 4 || f[0].size() != 1 || !strchr(sym ? "TWN" : "TW", f[0][0]) || !parse_hex128(s[1], tag) || (tag >> 64) || !parse_hex128(s[2], ed) ||
+            !hs::fe_from_hex(x, f[1]) || !parse_hex128(f[2], d)) return 2;
+        const uint32_t type = (uint32_t)strtoul(s[4].c_str(), nullptr, 10);
+        if (type > 1u && !(sym && type == 3u)) return 2;
+        if (x.l[0] != (uint64_t)tag) { fprintf(stderr, "the record does not share the tag of the stored entry it is paired with\n"); return 2; }
+        const uint32_t flags = f[0] == "W" ? BSGS_KANGAROO_WILD : f[0] == "N" ? BSGS_KANGAROO_WILD | BSGS_KANGAROO_NEG : 0u;
+        Scalar key;
+        switch (tab.add_pair(ed, (uint32_t)strtoul(s[3].c_str(), nullptr, 10), type, d, (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, &key)) {
+        case KangarooTable::NEW: return 1;                            // (never: a pair is judged, not stored)
+        case KangarooTable::FOUND: printf("found %s\n", hs::fe_to_hex(key).c_str()); break;
+        case KangarooTable::RESEED: printf("reseed %s\n", f[3].c_str()); break;
+        case KangarooTable::FALSE_MATCH: printf("false\n"); break;
+        case KangarooTable::REPEAT: printf("repeat\n"); break;
+        }
+    }
+    if (sym) printf("summary %zu %llu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds(), (unsigned long long)tab.cycles());
+    else printf("summary %zu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds());
+    return 0;
+}
+
+// -selftest kangaroo-dpdev-plan <pk hex> <pke hex> <CUs> <min launch> <dp or -1> <kn or 0> <kdpn or 0>: the plan of -kdpdev for one engine without a GPU, one line:
+// "plan <dp> <kn> <per thread> <S> <record buffer> <capacity>"
+int kangaroo_dpdev_plan_selftest(const std::vector<std::string> &a)
+{
+    if (a.size() != 7) return 2;
+    KangConfig c;
+    c.pk = a[0]; c.pke = a[1];
+    Prologue p(c);
+    const int cus = atoi(a[2].c_str()), dp_arg = atoi(a[4].c_str());
+    const uint64_t capacity = dpdev_capacity(p.sqrtW, strtoull(a[6].c_str(), nullptr, 0));
+    Plan pl = plan_herd(p.sqrtW, 1, cus, dp_arg >= 0 ? dp_arg : (int)dpdev_dp(p.sqrtW, capacity), strtoull(a[5].c_str(), nullptr, 0));
+    plan_launch(pl, p.sqrtW, 0.0, atof(a[3].c_str()), true, dp_arg < 0);
+    printf("plan %u %llu %u %u %u %llu\n", pl.dp, (unsigned long long)pl.kn, pl.G, pl.S, pl.cap, (unsigned long long)capacity);
+    return 0;
+}
+
 // -selftest kangaroo-table-roundtrip <pk hex> <pke hex> <pubkey> <split> <record>...: the first <split> records into a table, the table into a work file
 // without herds (a temporary file; BSGS_SELFTEST_WORK names a path to write and keep instead), the file into a fresh table, the other records into that one.
 // Prints what -selftest kangaroo prints for the undivided stream.
@@ -275,6 +341,8 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-ktn") { c.ktn = strtoull(next().c_str(), nullptr, 0); if (!c.ktn || c.ktn > (1ull << 31)) die("-ktn must be 1..2^31"); }
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
+        else if (a == "-kdpdev") c.kdpdev = true;
+        else if (a == "-kdpn") { c.kdpn = strtoull(next().c_str(), nullptr, 0); if (!c.kdpn || c.kdpn > (1ull << 31)) die("-kdpn must be 1..2^31"); }
         else if (a == "-ksym") ksym = true;
         else if (a == "-kwalk") { const std::string w = next(); if (w != "plain" && w != "sym") die("-kwalk must be plain or sym"); kwalk_sym = w == "sym"; }
         else if (a == "-noverify") c.verify = false;
@@ -282,6 +350,18 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-kjumpscale") { c.jumpscale = atof(next().c_str()); if (!(c.jumpscale >= 1.0 / 64 && c.jumpscale <= 64.0)) die("-kjumpscale must be 1/64..64"); }
         else if (a == "-w" || a == "-htsz" || a == "-onlygen") die("-kangaroo cannot be combined with " + a + " (no baby table)");
         else die("Unknown parameter with -kangaroo: " + a);
+    }
+    // -kdpdev: the table of distinguished points of the one-key search, plain and -ksym, in device memory; every refusal before any device is looked for
+    if (c.kdpn && !c.kdpdev) die("-kdpn belongs to -kdpdev (the capacity of the table in GPU memory)");
+    if (c.kdpdev) {
+        if (!c.infile.empty()) die("-kangaroo -kdpdev cannot be combined with -infile (the table in GPU memory pairs the records of one key)");
+        if (!c.ktames.empty() || !c.ktamesgen.empty() || !c.ktamesmerge.empty())
+            die("-kangaroo -kdpdev cannot be combined with -ktames, -ktamessym, -ktamesgen or -ktamesmerge (a tame table is matched or grown by calls of its own)");
+        if (c.devices.find(',') != std::string::npos) die("-kangaroo -kdpdev takes one -d entry (several engines would need one table for all of them)");
+        if (c.devices.empty()) {                                       // without -d a run takes every GPU of the machine: here it takes the first
+            c.devices = "0";
+            printf("Kangaroo -kdpdev: no -d given, one engine on GPU #0\n");
+        }
     }
     // a tame table (host_kangaroo_tames.cpp): made by the plain walk, or with -kwalk sym by the symmetric walk (file version 2); searched with -ktames,
     // a table of the symmetric walk with -ktamessym; never saved; every refusal before any device is looked for
@@ -344,12 +424,25 @@ Plan kang::plan_herd(double sqrtW, uint32_t engines, int cus, int dp_arg, uint64
     return pl;
 }
 
+uint64_t kang::dpdev_capacity(double sqrtW, uint64_t kdpn)
+{
+    if (kdpn) return kdpn;
+    uint64_t cap = 1ull << 16;
+    while (cap < (1ull << 27) && (double)cap < 4.0 * sqrtW) cap *= 2;
+    return cap;
+}
+uint32_t kang::dpdev_dp(double sqrtW, uint64_t capacity)
+{
+    return (uint32_t)std::min(32.0, std::max(0.0, std::ceil(std::log2(4.0 * sqrtW / (double)capacity))));
+}
+
 // ---- KeyMode: what the search of one key, plain or -ksym, puts behind the driver's seam ---------------------------------------------------------------
 namespace {
 struct KeyMode : Mode {
     KeyMode(const KangConfig &c, const Affine &P) : c(c), P(P)
     {
         if (c.sym) { version = WORK_VERSION_SYM; min_launch = 2.0 * BSGS_KANGAROO_CYCLE_WINDOW; }      // -ksym: a launch longer than the cycle window
+        if (c.kdpdev) { counts_records = false; bound_launch = true; dp_free = c.dp < 0; }             // -kdpdev: the launch counts, and is kept within the record buffer
     }
     std::string fingerprint(const Prologue &p, const WorkHeader &h) const override { return kangaroo_fingerprint(P, p.lo, p.hi, h); }
     bool before_devices(Prologue &p) override
@@ -362,6 +455,12 @@ struct KeyMode : Mode {
             jumpscale = p.wh.jumpscale = p.resume ? f.jumpscale : c.jumpscale != 0.0 ? c.jumpscale : KSYM_JUMPSCALE;
         }
         printf("Kangaroo range [%s, %s], width 2^%.2f\n", hs::fe_to_hex(p.lo).c_str(), hs::fe_to_hex(p.hi).c_str(), std::log2((double)p.W));
+        if (c.kdpdev && p.resume && f.engines != 1) die("Recovery file was made with other settings");      // (-kdpdev is one engine with one table)
+        if (c.kdpdev) {                                                // the table in device memory: its capacity, and the dp that fills at most half of it
+            capacity = dpdev_capacity(p.sqrtW, c.kdpn);
+            while (p.resume && capacity < 2 * f.table && capacity < (1ull << 31)) capacity *= 2;      // (a file that holds more than this run would plan for)
+            dp_fixed = c.dp >= 0 ? c.dp : (int)dpdev_dp(p.sqrtW, capacity);
+        }
         // -ksym: offsets are counted from the middle of the range, k'' = k - (a + W/2) (include/bsgs_hip.h "Kangaroo, symmetric walk")
         base = c.sym ? hs::sc_add(p.lo, hs::sc_from_u128(p.W / 2)) : p.lo;
         Q = hs::point_add(P, hs::affine_neg(hs::point_mul(hs::G, base)));
@@ -381,10 +480,23 @@ struct KeyMode : Mode {
     {
         table.reset(new KangarooTable(p.lo, p.W, P, c.sym));
         if (p.resume) {
-            if (!table->restore(p.wf.table.data(), p.wf.h.table, p.wf.h.false_matches, p.wf.h.reseeds)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
+            if (c.kdpdev) {                                            // the file's entries go to the device once they are verified (resumed()); tag 0 stays here
+                std::vector<uint8_t> own;
+                for (uint64_t i = 0; i < p.wf.h.table; i++) {
+                    const uint8_t *en = &p.wf.table[32 * i];
+                    uint64_t k64; uint32_t type;
+                    memcpy(&k64, en, 8); memcpy(&type, en + 28, 4);
+                    if (type > 1u && !(c.sym && type == 3u)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
+                    std::vector<uint8_t> &to = k64 ? pending : own;
+                    to.insert(to.end(), en, en + 32);
+                }
+                p.wf.table.swap(own);
+                dev_entries = pending.size() / 32;
+            }
+            if (!table->restore(p.wf.table.data(), p.wf.table.size() / 32, p.wf.h.false_matches, p.wf.h.reseeds)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
             std::vector<uint8_t>().swap(p.wf.table);
             table->set_cycles(p.wf.h.cycles);
-            printf("Resumed: %llu steps, %zu DPs\n", (unsigned long long)p.wf.h.steps, table->size());
+            printf("Resumed: %llu steps, %zu DPs\n", (unsigned long long)p.wf.h.steps, table_size());
         }
         p.t0 = Clock::now();
         // the host's comb: -kcpuseed, and Q at infinity (the key is -pk itself: no affine Q to hand to the kernel; the host's additions take it as it is)
@@ -434,9 +546,54 @@ struct KeyMode : Mode {
     const char *setup(bsgs_dev *dev) override
     {
         const Plan &pl = pro->pl;
-        return (c.sym ? bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)
-                      : bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)) == BSGS_OK ? nullptr : "bsgs_kangaroo_setup";
+        if ((c.sym ? bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)
+                   : bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)) != BSGS_OK) return "bsgs_kangaroo_setup";
+        if (c.kdpdev && bsgs_kangaroo_dptable_begin(dev, capacity) != BSGS_OK) return "bsgs_kangaroo_dptable_begin";
+        return nullptr;
     }
+    // -kdpdev: the walk, the insert and the pairing in device memory; only the hand-backs reach the collector, and the DP count is the walk's
+    int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &sh) override
+    {
+        if (!c.kdpdev) return Mode::launch(dev, e, steps, recs, cap, n, dropped, sh);
+        uint64_t seen = 0, entries = 0;
+        const int rc = bsgs_kangaroo_run_dptable(dev, steps, recs, cap, n, &seen, &entries, dropped, nullptr);
+        if (rc != BSGS_OK) return rc;
+        uint64_t dead = 0;
+        for (uint32_t i = 0; i < *n; i++) dead += recs[i].reserved != BSGS_KANGAROO_DPT_STORED && (recs[i].flags & BSGS_KANGAROO_DEAD);
+        sh.dps += seen - std::min(seen, dead);
+        dev_entries = entries;
+        return rc;
+    }
+    // -kdpdev -wl: the file's entries, verified, into the device table; a tag that occurs twice or finds no slot: the section does not load
+    std::string resumed(bsgs_dev *dev, uint32_t e, Shared &sh) override
+    {
+        (void)e; (void)sh;
+        if (!c.kdpdev || pending.empty()) return "";
+        uint64_t stored = 0, dup = 0, zero = 0, full = 0, entries = 0;
+        const auto ts = Clock::now();
+        if (bsgs_kangaroo_dptable_load(dev, (const bsgs_kangaroo_dp_entry *)pending.data(), pending.size() / 32, &stored, &dup, &zero, &full, &entries) != BSGS_OK)
+            return std::string("bsgs_kangaroo_dptable_load: ") + bsgs_last_error();
+        if (dup || full || zero) return "-kangaroo -wl: the table section of " + pro->wl_path + " does not load";
+        printf("[startup] %-44s %.3fs\n", ("table (GPU memory), " + std::to_string(entries) + " entries").c_str(), since(ts));
+        dev_entries = entries;
+        std::vector<uint8_t>().swap(pending);
+        return "";
+    }
+    // -kdpdev: the device table as it stands, for save()
+    std::string fetch(bsgs_dev *dev, uint32_t e, Shared &sh) override
+    {
+        (void)e; (void)sh;
+        if (!c.kdpdev) return "";
+        uint64_t n = 0;
+        if (bsgs_kangaroo_dptable_read(dev, nullptr, 0, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();      // the count alone
+        std::vector<uint8_t> got(32 * n);
+        if (n && bsgs_kangaroo_dptable_read(dev, (bsgs_kangaroo_dp_entry *)got.data(), n, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();
+        if (32 * n != got.size()) return "bsgs_kangaroo_dptable_read: the table changed between the count and the read";
+        std::lock_guard<std::mutex> lk(dev_m);
+        dev_table.swap(got);
+        return "";
+    }
+    size_t table_size() const { return table->size() + (size_t)dev_entries.load(); }      // "in the table": the host's entries and the device's
     // (a whole herd from the host's comb was computed in prepare() and is uploaded by the driver: the comb is asked for lists only)
     const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) override
     {
@@ -466,7 +623,16 @@ struct KeyMode : Mode {
         u128 d;
         memcpy(&d, r.d, 16);
         Scalar k;
-        const KangarooTable::Verdict v = table->add(r.x, d, (uint32_t)(e * pro->pl.kn + r.kangaroo), r.flags, &k);
+        const uint32_t kid = (uint32_t)(e * pro->pl.kn + r.kangaroo);
+        KangarooTable::Verdict v;
+        if (c.kdpdev && r.reserved == BSGS_KANGAROO_DPT_STORED) { stored = r; have_stored = true; return true; }      // the entry the next record met
+        if (c.kdpdev && r.reserved == BSGS_KANGAROO_DPT_DUPLICATE) {
+            if (!have_stored) return true;                             // (never: the device does not split a pair)
+            have_stored = false;
+            u128 ed;
+            memcpy(&ed, stored.d, 16);
+            v = table->add_pair(ed, stored.kangaroo, stored.flags, d, kid, r.flags, &k);
+        } else v = table->add(r.x, d, kid, r.flags, &k);               // -kdpdev: DEAD, tag 0, a full device table -- the host's own map, as without the flag
         if (v == KangarooTable::FOUND) { key = k; found = true; sh.stop = true; return false; }
         if (v == KangarooTable::RESEED) sh.push_reseed(e, r.kangaroo);
         return true;
@@ -481,8 +647,11 @@ struct KeyMode : Mode {
     }
     const WorkKeys *save(WorkHeader &h, std::vector<uint8_t> &entries) override
     {
-        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.table = table->size(); h.cycles = table->cycles();
-        entries.reserve(32 * table->size());
+        std::lock_guard<std::mutex> lk(dev_m);
+        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.table = table->size() + dev_table.size() / 32; h.cycles = table->cycles();
+        entries.swap(dev_table);                                       // -kdpdev: what fetch() read when the herds were downloaded -- moved, not copied: every save
+        std::vector<uint8_t>().swap(dev_table);                        // follows a fetch() of its own
+        entries.reserve(entries.size() + 32 * table->size());
         table->write_entries(entries);
         return nullptr;
     }
@@ -500,6 +669,13 @@ struct KeyMode : Mode {
     bool cpuseed = false;
     std::unique_ptr<Comb> comb;
     std::vector<std::vector<i128>> off0;
+    // -kdpdev
+    uint64_t capacity = 0;                         // of the device table
+    std::atomic<uint64_t> dev_entries{0};          // entries in it after the last launch
+    std::vector<uint8_t> pending, dev_table;       // -wl: the file's entries on their way to the device; the device table as fetch() read it
+    std::mutex dev_m;
+    bsgs_kangaroo_record stored;                   // the first record of a handed-back pair, until its record comes
+    bool have_stored = false;
 };
 }  // namespace
 
@@ -516,7 +692,12 @@ int kangaroo_main(int argc, char **argv)
     p.complete(c, mode);
     const Plan &pl = p.pl;
     printf("Expected steps: 2^%.2f (2 sqrt(W) + DP overhead), expected DPs 2^%.2f\n", std::log2(pl.expected), std::log2(2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) + 1.0));
-    if (c.dp < 0 && 2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) > 67108864.0) printf("WARNING: the expected DP count exceeds 2^26 host entries even at -dp 32\n");
+    if (c.kdpdev) {
+        uint64_t slots = 128;
+        while (slots < 2 * (mode.capacity + pl.cap)) slots *= 2;
+        printf("Kangaroo: distinguished points stay in GPU memory (-kdpdev): table of %llu entries, %llu slots, %.2f GiB; hand-backs only cross the bus\n",
+               (unsigned long long)mode.capacity, (unsigned long long)slots, (double)slots * 32.0 / 1073741824.0);
+    } else if (c.dp < 0 && 2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) > 67108864.0) printf("WARNING: the expected DP count exceeds 2^26 host entries even at -dp 32\n");
     if (c.sym) printf("Kangaroo: symmetric walk (negation map), %u jump points, jump scale %g\n", p.wh.jumps, p.wh.jumpscale);
     Shared sh(p);
     mode.prepare(p, sh);
@@ -536,7 +717,7 @@ int kangaroo_main(int argc, char **argv)
     }
     char tail[512];
     snprintf(tail, sizeof tail, "Job time %.2fs, %.3e kangaroo steps, %llu DPs (%zu in the table, %llu dropped), %llu false matches, %llu re-seeds\n", secs,
-             (double)sh.steps.load(), (unsigned long long)sh.dps.load(), table.size(), (unsigned long long)sh.dropped.load(), (unsigned long long)table.false_matches(),
+             (double)sh.steps.load(), (unsigned long long)sh.dps.load(), mode.table_size(), (unsigned long long)sh.dropped.load(), (unsigned long long)table.false_matches(),
              (unsigned long long)table.reseeds());
     text += tail;
     if (c.sym) text += "Symmetric walk: " + std::to_string(table.cycles()) + " cycles retired\n";

@@ -80,6 +80,8 @@ struct KangConfig {
     std::string ktamesmerge;                       // -ktamesmerge A,B[,C...] with -ktamesgen: the tables are merged by tag on the host
     uint64_t ktnplan = 0;                          // -ktnplan N with -ktamesgen: the walk is planned for a table of N entries (0: for -ktn)
     bool range_given = false;                      // -pk or -pke stood on the command line
+    bool kdpdev = false;                           // -kdpdev with -pb, plain and -ksym: the table of distinguished points lives in device memory (bsgs_kangaroo_run_dptable)
+    uint64_t kdpn = 0;                             // -kdpn N with -kdpdev: the capacity of that table (default: dpdev_capacity)
 };
 KangConfig parse_kangaroo_args(int argc, char **argv);
 
@@ -87,6 +89,11 @@ struct Plan { uint32_t engines, dp, G, S, cap; uint64_t kn; double expected; };
 // defaults from W: expected DPs (2 sqrt(W) / 2^dp) within 2^25 host entries, DP overhead N_k 2^dp at most sqrt(W) / 8, a full herd is 16 kangaroos per
 // thread at four waves per SIMD; dp_arg < 0 / kn_arg == 0: chosen here.  S and cap are left to the caller (they depend on the expected total).
 Plan plan_herd(double sqrtW, uint32_t engines, int cus, int dp_arg, uint64_t kn_arg);
+// -kdpdev ("the table of distinguished points in device memory"): the capacity is -kdpn, or the power of two at or above 4 sqrt(W) within
+// [2^16, 2^27]; the default dp = max(0, ceil(log2(4 sqrt(W) / capacity))): the 2 sqrt(W) / 2^dp expected DPs fill at most half the capacity, a quarter of the
+// slots.  The herd then follows by plan_herd's rule, up to the full herd.
+uint64_t dpdev_capacity(double sqrtW, uint64_t kdpn);
+uint32_t dpdev_dp(double sqrtW, uint64_t capacity);
 
 // ---- the work file <dir>/kangaroo.work: version 1 the plain walk, 2 -ksym, 3 a list of keys (-infile), 4 a list with -kwalk sym --------
 const uint32_t WORK_VERSION = 1, WORK_VERSION_SYM = 2, WORK_VERSION_KEYS = 3;       // 2: written and read by -ksym only; the header continues behind the fingerprint

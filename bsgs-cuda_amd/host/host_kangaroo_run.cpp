@@ -32,6 +32,20 @@ std::vector<size_t> kang::comb_states(const Comb &C, const std::vector<i128> &d,
     return inf;
 }
 
+void kang::plan_launch(Plan &pl, double sqrtW, double expected0, double min_launch, bool bound, bool dp_free)
+{
+    const double Nk = (double)pl.kn * pl.engines, half = 2097152.0;
+    auto expected = [&]() { return (expected0 > 0.0 ? expected0 : 2.0 * sqrtW) + Nk * std::ldexp(1.0, (int)pl.dp); };
+    auto records = [&]() { return (double)pl.kn * pl.S / std::ldexp(1.0, (int)pl.dp); };
+    pl.expected = expected();
+    pl.S = (uint32_t)std::max(min_launch, std::min(1024.0, pl.expected / Nk / 8.0));
+    if (bound) {
+        if (records() > half) pl.S = (uint32_t)std::max(min_launch, std::floor(half * std::ldexp(1.0, (int)pl.dp) / (double)pl.kn));
+        while (dp_free && records() > half && pl.dp < 32) { pl.dp++; pl.expected = expected(); }
+    }
+    pl.cap = (uint32_t)std::min<double>(1u << 22, 2.0 * records() + 65536.0);
+}
+
 Prologue::Prologue(const KangConfig &c)
 {
     if (!hs::fe_from_hex(lo, c.pk) || hs::fe_is_zero(lo)) die("Start range can`t be zero");
@@ -89,9 +103,7 @@ void Prologue::complete(const KangConfig &c, Mode &mode)
     if (pl.kn > (1ull << 26)) die("-kn: at most 2^26 kangaroos per engine");
     mode.planned(*this);
     const double Nk = (double)pl.kn * pl.engines;
-    pl.expected = (mode.expected > 0.0 ? mode.expected : 2.0 * sqrtW) + Nk * std::ldexp(1.0, (int)pl.dp);
-    pl.S = (uint32_t)std::max(mode.min_launch, std::min(1024.0, pl.expected / Nk / 8.0));
-    pl.cap = (uint32_t)std::min<double>(1u << 22, 2.0 * (double)pl.kn * pl.S / std::ldexp(1.0, (int)pl.dp) + 65536.0);
+    plan_launch(pl, sqrtW, mode.expected, mode.min_launch, mode.bound_launch, mode.dp_free && !resume);
     uint64_t seed = c.seed;
     if (resume) seed = wf.h.seed;
     else if (!c.seed_given) { std::random_device rd; seed = ((uint64_t)rd() << 32) ^ rd(); }
@@ -234,6 +246,7 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
         sh.checked++;
         while (sh.checked.load() < p.pl.engines && !sh.stop.load()) std::this_thread::sleep_for(std::chrono::milliseconds(1));
     }
+    if (p.resume && ok && !sh.failed.load()) { const std::string msg = mode.resumed(dev, e, sh); if (!msg.empty()) { end_with(msg); ok = false; } }
     bool first_launch = true;
     std::vector<bsgs_kangaroo_record> recs(ok ? p.pl.cap : 0);
     while (ok) {
@@ -273,6 +286,8 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
         if (want) {
             sh.saved[e].resize(kn);
             if (bsgs_kangaroo_download(dev, 0, (uint32_t)kn, sh.saved[e].data()) != BSGS_OK) { bad("bsgs_kangaroo_download"); sh.saved[e].clear(); break; }
+            const std::string msg = mode.fetch(dev, e, sh);
+            if (!msg.empty()) { end_with(msg); sh.saved[e].clear(); break; }
         }
         if (stopped) break;
         if (want) {                                                    // parked: wait for the file
@@ -325,7 +340,7 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
             if (mode.done()) continue;
             sh.engine_records[b.first] += b.second.size();
             for (const bsgs_kangaroo_record &r : b.second) {
-                if (!(r.flags & BSGS_KANGAROO_DEAD)) sh.dps++;
+                if (mode.counts_records && !(r.flags & BSGS_KANGAROO_DEAD)) sh.dps++;
                 if (!mode.record(b.first, r, sh)) break;
             }
         }

@@ -72,6 +72,10 @@ public:
     double mean_jump = 0.0, expected = 0.0;
     const uint64_t *jump_scalars = nullptr;
     bool saves = true;
+    // a mode whose distinguished points stay in device memory (-kdpdev): the launch itself counts what the walk produced, so the collector does not count the
+    // records that come back; the launch is kept so short that the records it is expected to write fill at most half of the largest record buffer, and when
+    // the floor of the launch length does not do it, dp is raised as long as the command line (or a work file) has not fixed it
+    bool counts_records = true, bound_launch = false, dp_free = false;
     const char *herd_label = "herds (GPU), engine ";                  // the [startup] line of a herd seeded in its engine's thread
     virtual std::string fingerprint(const Prologue &p, const WorkHeader &h) const = 0;
     // between the work file and the devices: the mode's own resume checks ("Recovery file was made with other settings"), its header fields, its first
@@ -96,6 +100,12 @@ public:
     // in an engine's thread, after its last launch and before its device is closed (only when nothing failed): a mode that keeps something in device memory
     // fetches it here; "", or the message the run ends with
     virtual std::string ending(bsgs_dev *dev, uint32_t e, Shared &sh) { (void)dev; (void)e; (void)sh; return ""; }
+    // in an engine's thread, -wl only: after the herd and the saved table went through the verification (or -noverify skipped it) and before the first launch: a
+    // mode that keeps its table in device memory loads it here; "", or the message the run ends with
+    virtual std::string resumed(bsgs_dev *dev, uint32_t e, Shared &sh) { (void)dev; (void)e; (void)sh; return ""; }
+    // in an engine's thread, where its herd has been downloaded for a save (parked between two launches, or at the end of a search that is not done): a mode
+    // that keeps its table in device memory reads it into host memory here, so that save() writes what belongs to this moment; "", or the message
+    virtual std::string fetch(bsgs_dev *dev, uint32_t e, Shared &sh) { (void)dev; (void)e; (void)sh; return ""; }
     // what the verification needs (bsgs_kangaroo_verify, bsgs_kangaroo_verify_points; set in before_devices): the one Q of every wild kangaroo, or null: the
     // key list the engines got in setup(); why the device cannot check this search, or null; the flags a table entry's type or owner word stands for
     const uint8_t *verify_q = nullptr;
@@ -107,6 +117,11 @@ public:
     // the mode's part of a work file: the table's entries and counters, its own header fields; the key list's state or nullptr
     virtual const WorkKeys *save(WorkHeader &h, std::vector<uint8_t> &entries) = 0;
 };
+
+// the launch of a plan whose herd and dp stand: the expected total (expected0, or 2 sqrt(W) when that is 0, plus the DP overhead N_k 2^dp), S = an eighth of a
+// kangaroo's share of it within [min_launch, 1024], and the record buffer for twice the records a launch is expected to write (at most 2^22).  bound: S, then
+// dp (only when dp_free), give way until kn S / 2^dp is at most 2^21, half of the largest record buffer
+void plan_launch(Plan &pl, double sqrtW, double expected0, double min_launch, bool bound, bool dp_free);
 
 enum Outcome { DONE, GAVE_UP, BUDGET, INTERRUPTED, ENDED };           // ENDED: stopped for none of the other reasons
 // engines, collector, monitor, shutdown and the last save; the mode turns the outcome into its closing text and exit code

@@ -32,6 +32,7 @@ NATIVE_SYMBOLS = [
     "bsgs_kangaroo_tames_image", "bsgs_kangaroo_tames_install", "bsgs_kangaroo_run_tames", "bsgs_kangaroo_tames_install_keys", "bsgs_kangaroo_run_tames_keys",
     "bsgs_kangaroo_tames_gen_begin", "bsgs_kangaroo_run_tames_gen", "bsgs_kangaroo_tames_gen_insert", "bsgs_kangaroo_tames_gen_read", "bsgs_kangaroo_tames_gen_end",
     "bsgs_kangaroo_tames_gen_load", "bsgs_kangaroo_tames_gen_read_sorted",
+    "bsgs_kangaroo_dptable_begin", "bsgs_kangaroo_run_dptable", "bsgs_kangaroo_dptable_insert", "bsgs_kangaroo_dptable_load", "bsgs_kangaroo_dptable_read", "bsgs_kangaroo_dptable_end",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
@@ -78,6 +79,7 @@ FE3_INV_BLOCK_KANG, FE3_INV_BLOCK_SEED, FE3_INV_BLOCK_TILE, FE3_INV_BLOCK2_TILE,
 KANGAROO_JUMPS, KANGAROO_WILD, KANGAROO_DEAD = 64, 1, 0x80000000
 KANGAROO_NEG, KANGAROO_CYCLE = 2, 4                # the symmetric walk (kangaroo_setup_sym)
 KANGAROO_GEN_DEAD, KANGAROO_GEN_DUPLICATE, KANGAROO_GEN_TAG_ZERO, KANGAROO_GEN_FULL = range(4)   # why the growing tame table hands a record back
+KANGAROO_DPT_DEAD, KANGAROO_DPT_DUPLICATE, KANGAROO_DPT_TAG_ZERO, KANGAROO_DPT_FULL, KANGAROO_DPT_STORED = range(5)   # the distinguished-point table's hand-backs
 KANGAROO_KEY_SHIFT, KANGAROO_MAX_KEYS = 8, 65535   # many keys in one herd (kangaroo_set_keys): a wild kangaroo's key index, 16 bits of its flags
 
 _lib = None
@@ -206,6 +208,14 @@ def lib():
             "bsgs_kangaroo_tames_gen_end": [vp],
             "bsgs_kangaroo_tames_gen_load": [vp, vp, vp, C.c_uint64] + [C.POINTER(C.c_uint64)] * 5,
             "bsgs_kangaroo_tames_gen_read_sorted": [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)],
+            "bsgs_kangaroo_dptable_begin": [vp, C.c_uint64],
+            "bsgs_kangaroo_run_dptable": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_float)],
+            "bsgs_kangaroo_dptable_insert": [vp, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64)],
+            "bsgs_kangaroo_dptable_load": [vp, vp, C.c_uint64] + [C.POINTER(C.c_uint64)] * 5,
+            "bsgs_kangaroo_dptable_read": [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)],
+            "bsgs_kangaroo_dptable_end": [vp],
             "bsgs_kangaroo_run_tames_keys": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_float)],
         }
@@ -848,6 +858,67 @@ class Device:
         if raw:
             return (tb, db), n.value
         return [(int.from_bytes(tb[8 * k:8 * k + 8], "little"), int.from_bytes(db[16 * k:16 * k + 16], "little")) for k in range(got)], n.value
+
+    # ---- the distinguished-point table in device memory (include/bsgs_hip.h "Kangaroo, distinguished-point table in device memory")
+    def kangaroo_dptable_begin(self, capacity):
+        """allocates the table for `capacity` entries under the herd of kangaroo_setup / kangaroo_setup_sym; replaces an earlier one"""
+        _chk(self.L.bsgs_kangaroo_dptable_begin(self.h, capacity))
+
+    def kangaroo_run_dptable(self, steps, max_recs=None):
+        """one launch of `steps` steps inserted into the table on the device: (hand-backs, n_seen, n_entries, dropped, kernel ms); a hand-back is
+        kangaroo_run's record with "reason" (KANGAROO_DPT_*) in the place of "key", and a duplicate is two of them: the stored entry (reason
+        KANGAROO_DPT_STORED, x = its tag, flags = its type), then the walk's record; max_recs: a host buffer of another size than two per record"""
+        cap = 2 * self._kang_cap if max_recs is None else max_recs
+        recs = (KangarooRecord * max(1, cap))()
+        n, seen, entries, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _chk(self.L.bsgs_kangaroo_run_dptable(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
+        return self._gen_handed_back(recs, n.value), seen.value, entries.value, dropped.value, ms.value
+
+    def kangaroo_dptable_insert(self, records, max_recs=None):
+        """insert and resolve alone on records of the caller's, (tag or x, d, flags[, kangaroo]) each: (hand-backs, n_entries, dropped)"""
+        m = len(records)
+        arr = (KangarooRecord * max(1, m))()
+        for k, (x, d, fl, *kang) in enumerate(records):
+            arr[k].x[:] = le32(x)
+            arr[k].d[:] = (d % (1 << 128)).to_bytes(16, "little")
+            arr[k].flags = fl
+            arr[k].kangaroo = kang[0] if kang else k
+        cap = 2 * self._kang_cap if max_recs is None else max_recs
+        out = (KangarooRecord * max(1, cap))()
+        n, entries, dropped = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _chk(self.L.bsgs_kangaroo_dptable_insert(self.h, arr, m, out, cap, C.byref(n), C.byref(entries), C.byref(dropped)))
+        return self._gen_handed_back(out, n.value), entries.value, dropped.value
+
+    def kangaroo_dptable_load(self, entries):
+        """entries (tag, d mod 2^128, kangaroo, type), or the bytes of n 32-byte entries, into the table -> (stored, duplicate, zero, full, n_entries)"""
+        raw = bytes(entries) if isinstance(entries, (bytes, bytearray, memoryview)) else b"".join(
+            t.to_bytes(8, "little") + (d % (1 << 128)).to_bytes(16, "little") + k.to_bytes(4, "little") + ty.to_bytes(4, "little") for t, d, k, ty in entries)
+        n = len(raw) // 32
+        assert len(raw) == 32 * n
+        out = [C.c_uint64() for _ in range(5)]
+        _chk(self.L.bsgs_kangaroo_dptable_load(self.h, C.c_char_p(raw), n, *[C.byref(v) for v in out]))
+        return tuple(v.value for v in out)
+
+    def kangaroo_dptable_read(self, max_entries=None, raw=False):
+        """the table's entries as a list of (tag, d mod 2^128, kangaroo, type), in any order; max_entries: the room offered (None: what the table holds);
+        raw: the bytes of the 32-byte entries in the place of the list"""
+        n = C.c_uint64()
+        if max_entries is None:
+            rc = self.L.bsgs_kangaroo_dptable_read(self.h, None, 0, C.byref(n))
+            if n.value == 0:
+                _chk(rc)
+                return b"" if raw else []
+            max_entries = n.value
+        buf = C.create_string_buffer(32 * max(1, max_entries))
+        _chk(self.L.bsgs_kangaroo_dptable_read(self.h, buf, max_entries, C.byref(n)))
+        b = buf.raw[:32 * n.value]
+        if raw:
+            return b
+        return [(int.from_bytes(b[o:o + 8], "little"), int.from_bytes(b[o + 8:o + 24], "little"), int.from_bytes(b[o + 24:o + 28], "little"),
+                 int.from_bytes(b[o + 28:o + 32], "little")) for o in range(0, len(b), 32)]
+
+    def kangaroo_dptable_end(self):
+        _chk(self.L.bsgs_kangaroo_dptable_end(self.h))
 
     def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):
         """start points on the GPU: kangaroo idx[k] (first + k without idx) := (d*G or Q + d*G, d, flags[k]) for d = offsets[k] (a signed integer) and

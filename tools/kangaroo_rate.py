@@ -2,7 +2,7 @@
 """Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
-    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--no-vgprs] [--out FILE]
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--dptable N] [--no-vgprs] [--out FILE]
     tools/kangaroo_rate.py --tamesload N | --tamessort N [--reps 3] [--out FILE]
 
 --sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch); with --keys
@@ -15,6 +15,11 @@ With --sym --keys the table is that of the keyed herd (bsgs_kangaroo_tames_insta
 --tamesgen N begins a growing tame table of capacity N (bsgs_kangaroo_tames_gen_begin) under an all-tame herd of pairwise different starts (seeded on the
 GPU: repeated starts would make every record a duplicate) and times bsgs_kangaroo_run_tames_gen and bsgs_kangaroo_run in turn, launch by launch, in one
 process: the difference of their kernel times is the insert.  Plain walk, or with --sym the symmetric one (the generators of -ktamesgen -ktamesdev).
+
+--dptable N begins a distinguished-point table of capacity N in device memory (bsgs_kangaroo_dptable_begin) under a herd of pairwise different starts, half
+tame and half wild (seeded on the GPU), and times bsgs_kangaroo_run_dptable and bsgs_kangaroo_run in turn, launch by launch, in one process: the difference
+of their kernel times is insert + resolve.  Plain walk, or with --sym the symmetric one: the search of -kdpdev.  Choose --steps and --dp so that a launch
+writes at most 2^22 records (a full herd at --dp 7: --steps 64).
 
 --tamesload N times bsgs_kangaroo_tames_gen_load of N synthetic entries (pairwise different tags, 24 bytes each from pageable host memory) into a fresh growing
 table of capacity N, --reps times.  --tamessort N loads such a table once and times bsgs_kangaroo_tames_gen_read_sorted of all N entries (harvest, radix sort,
@@ -125,6 +130,7 @@ def main():
     ap.add_argument("--keys", action="store_true")
     ap.add_argument("--tames", type=int, default=0)
     ap.add_argument("--tamesgen", type=int, default=0)
+    ap.add_argument("--dptable", type=int, default=0)
     ap.add_argument("--tamesload", type=int, default=0)
     ap.add_argument("--tamessort", type=int, default=0)
     ap.add_argument("--reps", type=int, default=3)
@@ -135,6 +141,8 @@ def main():
         ap.error("--keys goes with --sym")
     if a.tamesgen and (a.keys or a.tames):
         ap.error("--tamesgen goes with the plain walk or --sym alone")
+    if a.dptable and (a.keys or a.tames or a.tamesgen):
+        ap.error("--dptable goes with the plain walk or --sym alone")
     if a.tamesload or a.tamessort:
         return table_legs(a)
     dev = pybsgs.Device(0)
@@ -199,6 +207,49 @@ def main():
                "ms_walk_each": plain, "ms_walk_and_insert_each": both,
                "records_per_launch": nrec / a.launches, "records_handed_back_per_launch": back / a.launches, "dropped": dr, "entries": n_entries.value,
                "steps_per_s_kernel_walk": n * a.steps / (sum(plain) / len(plain) / 1e3), "steps_per_s_kernel_walk_and_insert": n * a.steps / (sum(both) / len(both) / 1e3)}
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        dev.close()
+        return
+
+    if a.dptable:
+        import numpy as np
+        d = np.random.RandomState(7).randint(1, 1 << 62, size=(n, 2), dtype=np.uint64)
+        d[:, 1] &= np.uint64((1 << 36) - 1)                          # offsets below 2^100, pairwise different but for a 2^-62 chance
+        flags = (C.c_uint32 * n)(*([0] * (n // 2) + [pybsgs.KANGAROO_WILD] * (n - n // 2)))
+        q = mul(0xD15C0 << 70)
+        pybsgs._chk(L.bsgs_kangaroo_seed(dev.h, pybsgs.le32(q[0]) + pybsgs.le32(q[1]), None, 0, n, d.tobytes(), flags, None, None))
+        t0 = time.perf_counter()
+        pybsgs._chk(L.bsgs_kangaroo_dptable_begin(dev.h, a.dptable))
+        begin_s = time.perf_counter() - t0
+        seen, n_entries = C.c_uint64(), C.c_uint64()
+
+        def launch_dpt():
+            pybsgs._chk(L.bsgs_kangaroo_run_dptable(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(n_entries), C.byref(dropped), C.byref(ms)))
+            return ms.value, seen.value, cnt.value
+
+        for _ in range(a.warmup):
+            launch()
+            launch_dpt()
+        plain, both, nrec, back, dr = [], [], 0, 0, 0
+        for _ in range(a.launches):
+            plain.append(launch()[0])
+            k, r, m = launch_dpt()
+            both.append(k)
+            nrec += r
+            back += m
+            dr += dropped.value
+        ins = (sum(both) - sum(plain)) / len(both)
+        res = {"what": "kangaroo walk with the distinguished-point table in device memory, one engine, full herd, half tame half wild" + (", symmetric walk" if a.sym else ""),
+               "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp, "launches": a.launches, "capacity": a.dptable,
+               "slots": 1 << max(7, (2 * (a.dptable + (1 << 22)) - 1).bit_length()), "begin_s": begin_s,
+               "ms_per_launch_walk": sum(plain) / len(plain), "ms_per_launch_walk_insert_resolve": sum(both) / len(both), "ms_insert_resolve": ins,
+               "insert_resolve_share": ins / (sum(both) / len(both)), "ms_walk_each": plain, "ms_walk_insert_resolve_each": both,
+               "records_per_launch": nrec / a.launches, "records_handed_back_per_launch": back / a.launches, "dropped": dr, "entries": n_entries.value,
+               "steps_per_s_kernel_walk": n * a.steps / (sum(plain) / len(plain) / 1e3), "steps_per_s_kernel_walk_insert_resolve": n * a.steps / (sum(both) / len(both) / 1e3)}
         line = json.dumps(res)
         print(line)
         if a.out:
