@@ -19,7 +19,18 @@ int bsgs_fail(int code, const char *fmt, ...);
 // kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table, the staging of a seed call and the key list;
 // kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records;
 // kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer; kangaroo_tames_extend.hip: its load and sorted read;
-// kangaroo_dptable.hip: the distinguished-point table of a search with its own buffer of hand-backs
+// kangaroo_dptable.hip: the distinguished-point table of a search with its own buffer of hand-backs (both tables: KangTable)
+// the table in device memory (kangaroo_table.hip.h has the rule): tag[slots] (0 = empty), the offset of each, its owner (kangaroo, type; null for the tame
+// table), eight counters.  It exists where tag is set; slots is a power of two
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+struct KangTable {
+    u64 *tag = nullptr;
+    u32x4 *d = nullptr;
+    u32x2 *who = nullptr;
+    u64 *ctr = nullptr;
+    uint64_t slots = 0;
+};
+
 struct bsgs_kangaroo {
     u32x4 *st = nullptr, *chain = nullptr, *table = nullptr, *staging = nullptr;
     u32 *flags = nullptr, *rec = nullptr, *idx = nullptr;
@@ -41,16 +52,9 @@ struct bsgs_kangaroo {
     u32x4 *tames = nullptr;                // bsgs_kangaroo_tames_install: the image, tames_lines lines of 64 bytes (a power of two), tames_n entries
     u32 *tames_rec = nullptr;              // the records of a launch that matched, laid out as rec
     uint64_t tames_lines = 0, tames_n = 0;
-    u64 *gen_tag = nullptr;                // bsgs_kangaroo_tames_gen_begin: gen_slots tags (a power of two; 0 = empty) ...
-    u32x4 *gen_d = nullptr;                // ... and the offset of each
-    u64 *gen_ctr = nullptr;                // eight words: entries in the table, occupied slots met by the last harvest; kangaroo_tames_extend.hip: the four counts of a load, OR and AND of the tags
-    uint64_t gen_slots = 0;
-    u64 *dpt_tag = nullptr;                // bsgs_kangaroo_dptable_begin (kangaroo_dptable.hip): dpt_slots tags (a power of two; 0 = empty) ...
-    u32x4 *dpt_d = nullptr;                // ... the offset of each ...
-    u32 *dpt_who = nullptr;                // ... and its owner: kangaroo, type (two words per slot)
-    u32 *dpt_out = nullptr;                // the hand-backs of a launch: u64 places taken, u64 records handed back | 2 * cap records from byte 64
-    u64 *dpt_ctr = nullptr;                // eight words: entries in the table, occupied slots met by the last harvest, the four counts of a load
-    uint64_t dpt_slots = 0;
+    KangTable gen;                         // bsgs_kangaroo_tames_gen_begin: the tame table that grows during generation (no owners)
+    KangTable dpt;                         // bsgs_kangaroo_dptable_begin: the distinguished-point table of a search
+    u32 *dpt_out = nullptr;                // its hand-backs of a launch: u64 places taken, u64 records handed back | 2 * cap records from byte 64
 };
 
 struct bsgs_dev {
@@ -206,6 +210,24 @@ int bsgs_kangaroo_launch(bsgs_dev *d, uint32_t steps);     // kangaroo.hip: the 
 int bsgs_kangaroo_finish(bsgs_dev *d, uint64_t *count, const u32 *other, uint64_t *other_count, float *kernel_ms);
 int bsgs_kangaroo_copy_out(bsgs_dev *d, const u32 *buf, uint64_t held, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *given);
 void bsgs_kangaroo_release(bsgs_dev *d);                     // kangaroo.hip: frees the herd (bsgs_dev_close, a new bsgs_kangaroo_setup)
+// kangaroo_tames_gen.hip: the host side of a KangTable, shared with kangaroo_tames_extend.hip and kangaroo_dptable.hip.  Texts of the caller's go into its errors.
+uint64_t bsgs_kang_table_slots(uint64_t capacity, uint32_t record_cap);
+void bsgs_kang_table_free(KangTable *t);
+// the herd that a table call needs -> *k; `herds`: what a keyed herd is told; `begin`: what a missing table is told (null: the call needs no table)
+int bsgs_kang_table_herd(bsgs_dev *d, bsgs_kangaroo **k, KangTable bsgs_kangaroo::*table, const char *herds, const char *begin);
+int bsgs_kangaroo_tames_gen_herd(bsgs_dev *d, bsgs_kangaroo **k, bool table);      // ... with the growing tame table's texts
+// allocate and zero: the arrays (owners: with who), *out of out_bytes where there is none; tags, counters and out's header zeroed, the stream drained, slots set.
+// On an error no table is left, whatever failed (*out stays), and *nomem tells a refused allocation from a failed call
+hipError_t bsgs_kang_table_begin(bsgs_dev *d, KangTable *t, uint64_t slots, bool owners, u32 **out, size_t out_bytes, bool *nomem);
+int bsgs_kang_table_entries(bsgs_dev *d, const KangTable *t, uint64_t *n_entries);
+// *n records of the caller's into the walk's record buffer, their count at its head, and the header of the hand-backs `out` zeroed; *n is the source of a
+// copy on the stream: the caller keeps it until it has drained the stream
+int bsgs_kang_table_stage(bsgs_dev *d, bsgs_kangaroo *k, u32 *out, const bsgs_kangaroo_record *recs, const uint64_t *n);
+// behind the chunks of a load (e: how they went): the counters read and handed out; they must add up to n (text: n, the sum)
+int bsgs_kang_table_loaded(bsgs_dev *d, const KangTable *t, hipError_t e, uint64_t n, uint64_t *n_stored, uint64_t *n_duplicate, uint64_t *n_zero, uint64_t *n_full,
+                           uint64_t *n_entries, const char *text);
+// behind a harvest (its caller has zeroed ctr[CTR_MET] before it): what it met against the entries counted (`what`: the table's name in the error)
+int bsgs_kang_table_met_check(uint64_t met, uint64_t entries, const char *what);
 // hand a finished "lines + overflow list" table to the engine (it becomes the owner of both buffers)
 int bsgs_install_lines(bsgs_dev *d, u32x4 *lines, int lplog, u64 *ovf, uint64_t ovf_n, uint64_t ht_items, uint64_t w,
                        uint64_t overflow_buckets);

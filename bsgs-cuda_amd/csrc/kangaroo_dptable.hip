@@ -1,38 +1,20 @@
 // kangaroo_dptable.hip -- the distinguished-point table of a search, kept in device memory (include/bsgs_hip.h, "Kangaroo, distinguished-point table in device
 // memory"; tests/kangaroo_dptable_model.py restates it).  The growing tame table of kangaroo_tames_gen.hip with the owner of every entry: a record
-// that meets a stored point comes back WITH that point, so the host can pair tame and wild without holding the table.  A unit of its own: no other unit's kernels change.
-//   table     open addressing with linear probing, nothing is ever deleted: tag[slots] (u64, the low 64 bits of x; 0 = empty), d[slots] (16-byte vectors, the
-//             offset as the record holds it) and who[slots] (u32 kangaroo, u32 type: 0 tame, 1 wild, 3 wild with NEG).  Home slot (tag >> 6) & (slots - 1).
-//   insert    one record per lane, a wave strides over the records.  DEAD and tag-0 records are handed back; every other record runs
-//             old = atomicCAS(&tag[s], 0, t) from its home slot on: 0 -- the slot is ours, d[s] and who[s] are written with one vector store each; t -- a
-//             duplicate, handed back as a PAIR of consecutive records: a placeholder that names the slot, then the record; else the next slot, wrapping, at most
-//             `slots` times (then handed back as FULL).  Hand-backs are compacted by __ballot with one atomic per wave for the places (a duplicate takes two) and
-//             one for the count; the entry counter is bumped once per wave too.  Vector stores only, every store bounded.  No LDS, no scratch.
-//   resolve   a second kernel on the same stream: every placeholder becomes the slot's (tag, d, kangaroo, type) as a record.
-//   coherence as kangaroo_tames_gen.hip: A SLOT'S TAG IS DECIDED ONLY BY THE RETURN VALUE OF THE COMPARE-AND-SWAP; no plain load of a tag ever concludes that a
-//             slot is empty (the insert and the load make no plain load of a tag at all); d[s] and who[s] are read only by a kernel launched after the one that
-//             wrote them -- the resolve, the harvest -- which is why the pairing is not done inside the insert.
-//   equal tags in one launch: which of them is stored is unspecified; exactly one is, every other comes back paired with it.
+// that meets a stored point comes back WITH that point, so the host can pair tame and wild without holding the table.  The table, its claim and the coherence
+// rule: kangaroo_table.hip.h; here who[slots] stands beside d[slots] (u32 kangaroo, u32 type: 0 tame, 1 wild, 3 wild with NEG).
+//   insert    one record per lane, a wave strides over the records.  DEAD and tag-0 records are handed back; every other record claims a slot: stored -- d[s]
+//             and who[s] are written with one vector store each; a duplicate -- handed back as a PAIR of consecutive records: a placeholder that names the
+//             slot, then the record; no slot -- handed back as FULL.  One reservation per wave for the places (a duplicate takes two) and one atomic for the
+//             count; the entry counter is bumped once per wave too.  Every store bounded.
+//   resolve   a second kernel on the same stream: every placeholder becomes the slot's (tag, d, kangaroo, type) as a record.  d[s] and who[s] are read only
+//             by a kernel launched after the one that wrote them, which is why the pairing is not done inside the insert.
+//   equal tags in one launch: every one but the stored one comes back paired with it.
 //   load      32-byte entries of the caller's by the same rule, staged in chunks; the four outcomes are counted, nothing else comes back.
-//   harvest   strides over the slots and compacts the occupied ones into 32-byte entries by ballot, in any order.
-#include "bsgs_internal.h"
+//   harvest   strides over the slots and compacts the occupied ones into 32-byte entries, in any order.
+#include "kangaroo_table.hip.h"
 
-#define DPT_MIN_SLOTS 128ull
-#define DPT_MAX_CAPACITY (1ull << 31)
-#define DPT_GRID_MAX 1024u                                  // blocks of the insert and the resolve: four per CU; a wave strides over the records
-#define DPT_SCAN_GRID_MAX 4096u                             // blocks of the load and the harvest
 #define DPT_LOAD_CHUNK BSGS_KANGAROO_DPT_LOAD_CHUNK
 #define DPT_KEEP 0xFFFFFFFFu                                // (not a reason: the record went into the table)
-
-// dpt_ctr (eight u64): entries in the table, occupied slots met by the last harvest, the four counts of a load
-#define CTR_ENTRIES 0
-#define CTR_MET 1
-#define CTR_STORED 2
-#define CTR_DUPLICATE 3
-#define CTR_ZERO 4
-#define CTR_FULL 5
-
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ u32 dpt_type(u32 flags) { return (flags & BSGS_KANGAROO_WILD) ? (flags & (BSGS_KANGAROO_WILD | BSGS_KANGAROO_NEG)) : 0u; }
 
@@ -42,7 +24,7 @@ struct DptArgs {
     u32x4 *d;              // [slots]
     u32x2 *who;            // [slots]
     u32 *out;              // the hand-backs: u64 places taken, u64 records handed back | records; `reserved` = BSGS_KANGAROO_DPT_*
-    u64 *ctr;              // dpt_ctr
+    u64 *ctr;              // the table's counters
     u64 slot_mask;
     u32 cap;               // records read at most
     u32 out_cap;           // places of `out`
@@ -68,50 +50,32 @@ __global__ void __launch_bounds__(256) kangaroo_dptable_insert_kernel(const DptA
             if (r3.y & BSGS_KANGAROO_DEAD) reason = BSGS_KANGAROO_DPT_DEAD;
             else if (tag == 0ull) reason = BSGS_KANGAROO_DPT_TAG_ZERO;
             else {
-                reason = BSGS_KANGAROO_DPT_FULL;
-                s = (tag >> 6) & A.slot_mask;
-                for (u64 it = 0; it <= A.slot_mask; it++) {
-                    const u64 old = atomicCAS((unsigned long long *)&A.tag[s], 0ull, (unsigned long long)tag);      // the only way a tag is read
-                    if (old == 0ull) {
-                        A.d[s] = recs[(u64)i * 4 + 2];
-                        A.who[s] = (u32x2){r3.x, dpt_type(r3.y)};
-                        stored = true;
-                        reason = DPT_KEEP;
-                        break;
-                    }
-                    if (old == tag) { reason = BSGS_KANGAROO_DPT_DUPLICATE; break; }
-                    s = (s + 1ull) & A.slot_mask;
-                }
+                const u32 got = kt_claim(A.tag, A.slot_mask, tag, s, [&](u64 at) {
+                    A.d[at] = recs[(u64)i * 4 + 2];
+                    A.who[at] = (u32x2){r3.x, dpt_type(r3.y)};
+                });
+                stored = got == CTR_STORED;                          // (the claim names its outcome by the counter a load gives it)
+                if (!stored) reason = got == CTR_DUPLICATE ? BSGS_KANGAROO_DPT_DUPLICATE : BSGS_KANGAROO_DPT_FULL;
             }
         }
-        const u64 ms = __ballot(stored);
-        if (ms && (int)lane == __builtin_ctzll(ms)) atomicAdd((unsigned long long *)&A.ctr[CTR_ENTRIES], (unsigned long long)__builtin_popcountll(ms));
+        kt_count(&A.ctr[CTR_ENTRIES], __ballot(stored), lane);
         const bool back = reason != DPT_KEEP, dup = reason == BSGS_KANGAROO_DPT_DUPLICATE;
-        const u64 m = __ballot(back), md = __ballot(dup);
-        if (m) {
-            u64 pos0 = 0;
-            const int leader = __builtin_ctzll(m);
-            if ((int)lane == leader) {
-                pos0 = atomicAdd((unsigned long long *)A.out, (unsigned long long)(__builtin_popcountll(m) + __builtin_popcountll(md)));
-                atomicAdd((unsigned long long *)A.out + 1, (unsigned long long)__builtin_popcountll(m));
+        const u64 md = __ballot(dup);
+        const u64 pos = kt_reserve(back, lane, (u64 *)A.out, (u32)__builtin_popcountll(md)) + (u64)__builtin_popcountll(md & ((1ull << lane) - 1));      // a duplicate takes two places
+        kt_count((u64 *)A.out + 1, __ballot(back), lane);
+        if (back && pos + (dup ? 1u : 0u) < A.out_cap) {             // the bound of every store: a pair goes in whole or not at all
+            u32x4 *o = (u32x4 *)((char *)A.out + KANG_REC_HEADER) + pos * 4;
+            if (dup) {                                               // the placeholder: the slot, for the resolve
+                o[0] = (u32x4){(u32)s, (u32)(s >> 32), 0, 0};
+                o[1] = (u32x4){0, 0, 0, 0};
+                o[2] = (u32x4){0, 0, 0, 0};
+                o[3] = (u32x4){0, 0, 0, BSGS_KANGAROO_DPT_STORED};
+                o += 4;
             }
-            pos0 = __shfl(pos0, leader);
-            const u64 below = (1ull << lane) - 1;
-            u64 pos = pos0 + (u64)__builtin_popcountll(m & below) + (u64)__builtin_popcountll(md & below);
-            if (back && pos + (dup ? 1u : 0u) < A.out_cap) {         // the bound of every store: a pair goes in whole or not at all
-                u32x4 *o = (u32x4 *)((char *)A.out + KANG_REC_HEADER) + pos * 4;
-                if (dup) {                                           // the placeholder: the slot, for the resolve
-                    o[0] = (u32x4){(u32)s, (u32)(s >> 32), 0, 0};
-                    o[1] = (u32x4){0, 0, 0, 0};
-                    o[2] = (u32x4){0, 0, 0, 0};
-                    o[3] = (u32x4){0, 0, 0, BSGS_KANGAROO_DPT_STORED};
-                    o += 4;
-                }
-                o[0] = r0;
-                o[1] = recs[(u64)i * 4 + 1];
-                o[2] = recs[(u64)i * 4 + 2];
-                o[3] = (u32x4){r3.x, r3.y, r3.z, reason};
-            }
+            o[0] = r0;
+            o[1] = recs[(u64)i * 4 + 1];
+            o[2] = recs[(u64)i * 4 + 2];
+            o[3] = (u32x4){r3.x, r3.y, r3.z, reason};
         }
     }
 }
@@ -141,7 +105,7 @@ struct DptLoadArgs {
     u64 *tag;              // [slots]
     u32x4 *d;              // [slots]
     u32x2 *who;            // [slots]
-    u64 *ctr;              // dpt_ctr
+    u64 *ctr;              // the table's counters
     u64 slot_mask;
     u32 n;
 };
@@ -156,30 +120,13 @@ __global__ void __launch_bounds__(256) kangaroo_dptable_load_kernel(const DptLoa
         if (i < A.n) {
             const u32x4 e0 = A.in[(u64)i * 2], e1 = A.in[(u64)i * 2 + 1];
             const u64 tag = ((u64)e0.y << 32) | e0.x;
-            if (tag == 0ull) what = CTR_ZERO;
-            else {
-                what = CTR_FULL;
-                u64 s = (tag >> 6) & A.slot_mask;
-                for (u64 it = 0; it <= A.slot_mask; it++) {
-                    const u64 old = atomicCAS((unsigned long long *)&A.tag[s], 0ull, (unsigned long long)tag);      // the only way a tag is read
-                    if (old == 0ull) {
-                        A.d[s] = (u32x4){e0.z, e0.w, e1.x, e1.y};
-                        A.who[s] = (u32x2){e1.z, e1.w};
-                        what = CTR_STORED;
-                        break;
-                    }
-                    if (old == tag) { what = CTR_DUPLICATE; break; }
-                    s = (s + 1ull) & A.slot_mask;
-                }
-            }
+            u64 s;
+            what = tag == 0ull ? CTR_ZERO : kt_claim(A.tag, A.slot_mask, tag, s, [&](u64 at) {
+                A.d[at] = (u32x4){e0.z, e0.w, e1.x, e1.y};
+                A.who[at] = (u32x2){e1.z, e1.w};
+            });
         }
-        for (u32 k = CTR_STORED; k <= CTR_FULL; k++) {
-            const u64 m = __ballot(what == k);
-            if (m && (int)lane == __builtin_ctzll(m)) {
-                atomicAdd((unsigned long long *)&A.ctr[k], (unsigned long long)__builtin_popcountll(m));
-                if (k == CTR_STORED) atomicAdd((unsigned long long *)&A.ctr[CTR_ENTRIES], (unsigned long long)__builtin_popcountll(m));
-            }
-        }
+        kt_count_outcomes(A.ctr, what, lane);
     }
 }
 
@@ -188,7 +135,7 @@ struct DptHarvestArgs {
     const u32x4 *d;        // [slots]
     const u32x2 *who;      // [slots]
     u32x4 *out;            // [max][2] entries as the load takes them
-    u64 *ctr;              // dpt_ctr: [CTR_MET] occupied slots met (zeroed by the caller)
+    u64 *ctr;              // the table's counters: [CTR_MET] occupied slots met (zeroed by the caller)
     u64 slots, max;
 };
 
@@ -201,19 +148,12 @@ __global__ void __launch_bounds__(256) kangaroo_dptable_harvest_kernel(const Dpt
         const u64 s = base + lane;
         const u64 t = s < A.slots ? A.tag[s] : 0ull;
         const bool occ = t != 0ull;
-        const u64 m = __ballot(occ);
-        if (m) {
-            u64 pos0 = 0;
-            const int leader = __builtin_ctzll(m);
-            if ((int)lane == leader) pos0 = atomicAdd((unsigned long long *)&A.ctr[CTR_MET], (unsigned long long)__builtin_popcountll(m));
-            pos0 = __shfl(pos0, leader);
-            const u64 pos = pos0 + (u64)__builtin_popcountll(m & ((1ull << lane) - 1));
-            if (occ && pos < A.max) {                                // the bound of every store
-                const u32x4 dd = A.d[s];
-                const u32x2 w = A.who[s];
-                A.out[pos * 2] = (u32x4){(u32)t, (u32)(t >> 32), dd.x, dd.y};
-                A.out[pos * 2 + 1] = (u32x4){dd.z, dd.w, w.x, w.y};
-            }
+        const u64 pos = kt_reserve(occ, lane, &A.ctr[CTR_MET], 0);
+        if (occ && pos < A.max) {                                    // the bound of every store
+            const u32x4 dd = A.d[s];
+            const u32x2 w = A.who[s];
+            A.out[pos * 2] = (u32x4){(u32)t, (u32)(t >> 32), dd.x, dd.y};
+            A.out[pos * 2 + 1] = (u32x4){dd.z, dd.w, w.x, w.y};
         }
     }
 }
@@ -221,17 +161,11 @@ __global__ void __launch_bounds__(256) kangaroo_dptable_harvest_kernel(const Dpt
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(bsgs_kangaroo_dp_entry) == 32, "table entry: 32 bytes");
 
-static uint64_t dpt_slots(uint64_t capacity, uint32_t record_cap)
-{
-    uint64_t slots = DPT_MIN_SLOTS;
-    while (slots < 2 * (capacity + record_cap)) slots *= 2;          // at most half full even after the last launch overshoots `capacity`
-    return slots;
-}
-
 static void dpt_free(bsgs_kangaroo *k)
 {
-    for (void *p : {(void *)k->dpt_tag, (void *)k->dpt_d, (void *)k->dpt_who, (void *)k->dpt_out, (void *)k->dpt_ctr}) if (p) (void)hipFree(p);
-    k->dpt_tag = nullptr; k->dpt_d = nullptr; k->dpt_who = nullptr; k->dpt_out = nullptr; k->dpt_ctr = nullptr; k->dpt_slots = 0;
+    bsgs_kang_table_free(&k->dpt);
+    if (k->dpt_out) (void)hipFree(k->dpt_out);
+    k->dpt_out = nullptr;
 }
 
 static inline uint32_t dpt_out_cap(const bsgs_kangaroo *k) { return 2u * k->cap; }      // every record of a launch a duplicate: two places each (cap <= 2^26)
@@ -240,22 +174,13 @@ static inline uint32_t dpt_out_cap(const bsgs_kangaroo *k) { return 2u * k->cap;
 static int dpt_insert(bsgs_dev *d, bsgs_kangaroo *k)
 {
     DptArgs A;
-    A.rec = k->rec; A.tag = k->dpt_tag; A.d = k->dpt_d; A.who = (u32x2 *)k->dpt_who; A.out = k->dpt_out; A.ctr = k->dpt_ctr; A.slot_mask = k->dpt_slots - 1;
+    A.rec = k->rec; A.tag = k->dpt.tag; A.d = k->dpt.d; A.who = k->dpt.who; A.out = k->dpt_out; A.ctr = k->dpt.ctr; A.slot_mask = k->dpt.slots - 1;
     A.cap = k->cap; A.out_cap = dpt_out_cap(k);
-    const u32 blocks = std::min((k->cap + 255u) / 256u, DPT_GRID_MAX);
+    const u32 blocks = std::min((k->cap + 255u) / 256u, KT_INSERT_GRID_MAX);
     hipLaunchKernelGGL(kangaroo_dptable_insert_kernel, dim3(blocks), dim3(256), 0, d->stream, A);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(kangaroo_dptable_resolve_kernel, dim3(blocks), dim3(256), 0, d->stream, A);
     HIPCHK(hipGetLastError());
-    return BSGS_OK;
-}
-
-static int dpt_entries(bsgs_dev *d, bsgs_kangaroo *k, uint64_t *n_entries)
-{
-    uint64_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, k->dpt_ctr + CTR_ENTRIES, 8, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    if (n_entries) *n_entries = n;
     return BSGS_OK;
 }
 
@@ -280,12 +205,8 @@ static int dpt_copy_out(bsgs_dev *d, bsgs_kangaroo *k, uint64_t places, bsgs_kan
 
 static int dpt_herd(bsgs_dev *d, bsgs_kangaroo **k, bool table)
 {
-    if (!d) return fail(BSGS_ERR_ARG, "null");
-    *k = d->kangaroo;
-    if (!*k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
-    if ((*k)->key) return fail(BSGS_ERR_STATE, "a distinguished-point table serves the herds of bsgs_kangaroo_setup and bsgs_kangaroo_setup_sym");
-    if (table && !(*k)->dpt_tag) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_dptable_begin first");
-    return BSGS_OK;
+    return bsgs_kang_table_herd(d, k, &bsgs_kangaroo::dpt, "a distinguished-point table serves the herds of bsgs_kangaroo_setup and bsgs_kangaroo_setup_sym",
+                                table ? "bsgs_kangaroo_dptable_begin first" : nullptr);
 }
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
@@ -293,30 +214,20 @@ extern "C" int bsgs_kangaroo_dptable_begin(bsgs_dev *d, uint64_t capacity)
 {
     bsgs_kangaroo *k = nullptr;
     if (int rc = dpt_herd(d, &k, false)) return rc;
-    if (!capacity || capacity > DPT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "distinguished-point table of %llu entries: 1..2^31", (unsigned long long)capacity);
+    if (!capacity || capacity > KT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "distinguished-point table of %llu entries: 1..2^31", (unsigned long long)capacity);
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipStreamSynchronize(d->stream));
     dpt_free(k);
-    const uint64_t slots = dpt_slots(capacity, k->cap);
+    const uint64_t slots = bsgs_kang_table_slots(capacity, k->cap);
     const size_t out_bytes = KANG_REC_HEADER + (size_t)dpt_out_cap(k) * 64;
-    hipError_t e = hipMalloc(&k->dpt_tag, (size_t)slots * 8);
-    if (e == hipSuccess) e = hipMalloc(&k->dpt_d, (size_t)slots * 16);
-    if (e == hipSuccess) e = hipMalloc(&k->dpt_who, (size_t)slots * 8);
-    if (e == hipSuccess) e = hipMalloc(&k->dpt_ctr, 64);
-    if (e == hipSuccess) e = hipMalloc(&k->dpt_out, out_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        dpt_free(k);
+    bool nomem = false;
+    const hipError_t e = bsgs_kang_table_begin(d, &k->dpt, slots, true, &k->dpt_out, out_bytes, &nomem);
+    if (e != hipSuccess) dpt_free(k);                                // (the hand-backs' buffer too)
+    if (nomem)
         return fail(BSGS_ERR_NOMEM, "distinguished-point table of %llu entries: %llu slots need %llu bytes of tags, %llu of offsets, %llu of owners and %llu of records (%s)",
                     (unsigned long long)capacity, (unsigned long long)slots, (unsigned long long)(slots * 8), (unsigned long long)(slots * 16), (unsigned long long)(slots * 8),
                     (unsigned long long)out_bytes, hipGetErrorString(e));
-    }
-    e = hipMemsetAsync(k->dpt_tag, 0, (size_t)slots * 8, d->stream);              // empty = tag 0; offset and owner are read only where a tag stands
-    if (e == hipSuccess) e = hipMemsetAsync(k->dpt_ctr, 0, 64, d->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(k->dpt_out, 0, KANG_REC_HEADER, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    if (e != hipSuccess) { dpt_free(k); HIPCHK(e); }                               // no table is left, whatever failed
-    k->dpt_slots = slots;
+    HIPCHK(e);
     return BSGS_OK;
 }
 
@@ -340,7 +251,7 @@ extern "C" int bsgs_kangaroo_run_dptable(bsgs_dev *d, uint32_t steps, bsgs_kanga
     uint32_t give = 0;
     uint64_t kept = 0;
     if (int rc = dpt_copy_out(d, k, places, recs, max_recs, &give, &kept)) return rc;
-    if (int rc = dpt_entries(d, k, n_entries)) return rc;
+    if (int rc = bsgs_kang_table_entries(d, &k->dpt, n_entries)) return rc;
     *nrecs = give;
     if (n_seen) *n_seen = count;
     if (dropped) *dropped = (count - held) + (back - kept);          // never inserted, and handed back but not handed over (a pair counts once)
@@ -353,13 +264,8 @@ extern "C" int bsgs_kangaroo_dptable_insert(bsgs_dev *d, const bsgs_kangaroo_rec
     if (!d || !nrecs || (n && !recs_in)) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
     if (int rc = dpt_herd(d, &k, true)) return rc;
-    if (n > k->cap) return fail(BSGS_ERR_ARG, "%u records: at most the record capacity %u", n, k->cap);
-    HIPCHK(hipSetDevice(d->id));
     const uint64_t count = n;
-    HIPCHK(hipMemsetAsync(k->dpt_out, 0, KANG_REC_HEADER, d->stream));
-    HIPCHK(hipMemsetAsync(k->rec, 0, KANG_REC_HEADER, d->stream));
-    HIPCHK(hipMemcpyAsync(k->rec, &count, 8, hipMemcpyHostToDevice, d->stream));
-    if (n) HIPCHK(hipMemcpyAsync((char *)k->rec + KANG_REC_HEADER, recs_in, (size_t)n * 64, hipMemcpyHostToDevice, d->stream));      // into the walk's record buffer
+    if (int rc = bsgs_kang_table_stage(d, k, k->dpt_out, recs_in, &count)) return rc;
     if (int rc = dpt_insert(d, k)) return rc;
     uint64_t head[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(head, k->dpt_out, 16, hipMemcpyDeviceToHost, d->stream));
@@ -371,7 +277,7 @@ extern "C" int bsgs_kangaroo_dptable_insert(bsgs_dev *d, const bsgs_kangaroo_rec
     if (int rc = dpt_copy_out(d, k, places, recs_out, max_recs, &give, &kept)) return rc;
     *nrecs = give;
     if (dropped) *dropped = back - kept;
-    return dpt_entries(d, k, n_entries);
+    return bsgs_kang_table_entries(d, &k->dpt, n_entries);
 }
 
 extern "C" int bsgs_kangaroo_dptable_load(bsgs_dev *d, const bsgs_kangaroo_dp_entry *entries, uint64_t n, uint64_t *n_stored, uint64_t *n_duplicate, uint64_t *n_zero,
@@ -380,9 +286,9 @@ extern "C" int bsgs_kangaroo_dptable_load(bsgs_dev *d, const bsgs_kangaroo_dp_en
     if (!d || (n && !entries)) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
     if (int rc = dpt_herd(d, &k, true)) return rc;
-    if (n > DPT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "%llu entries to load: at most 2^31", (unsigned long long)n);
+    if (n > KT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "%llu entries to load: at most 2^31", (unsigned long long)n);
     HIPCHK(hipSetDevice(d->id));
-    HIPCHK(hipMemsetAsync(k->dpt_ctr + CTR_STORED, 0, 32, d->stream));
+    HIPCHK(hipMemsetAsync(k->dpt.ctr + CTR_STORED, 0, 32, d->stream));
     u32x4 *stage = nullptr;
     const uint64_t chunk = std::min<uint64_t>(n, DPT_LOAD_CHUNK);
     if (chunk) {
@@ -399,26 +305,16 @@ extern "C" int bsgs_kangaroo_dptable_load(bsgs_dev *d, const bsgs_kangaroo_dp_en
         e = hipMemcpyAsync(stage, entries + at, (size_t)m * 32, hipMemcpyHostToDevice, d->stream);
         if (e != hipSuccess) break;
         DptLoadArgs A;
-        A.in = stage; A.tag = k->dpt_tag; A.d = k->dpt_d; A.who = (u32x2 *)k->dpt_who; A.ctr = k->dpt_ctr; A.slot_mask = k->dpt_slots - 1; A.n = (u32)m;
-        const u32 blocks = (u32)std::min<uint64_t>((m + 255u) / 256u, DPT_SCAN_GRID_MAX);
+        A.in = stage; A.tag = k->dpt.tag; A.d = k->dpt.d; A.who = k->dpt.who; A.ctr = k->dpt.ctr; A.slot_mask = k->dpt.slots - 1; A.n = (u32)m;
+        const u32 blocks = (u32)std::min<uint64_t>((m + 255u) / 256u, KT_SCAN_GRID_MAX);
         hipLaunchKernelGGL(kangaroo_dptable_load_kernel, dim3(blocks), dim3(256), 0, d->stream, A);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(d->stream);    // the caller's buffer is pageable: the stage is free again
     }
-    uint64_t c[8] = {0};
-    if (e == hipSuccess) e = hipMemcpyAsync(c, k->dpt_ctr, 64, hipMemcpyDeviceToHost, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    const int rc = bsgs_kang_table_loaded(d, &k->dpt, e, n, n_stored, n_duplicate, n_zero, n_full, n_entries,
+                                          "distinguished-point table: %llu entries to load, %llu accounted for");
     if (stage) (void)hipFree(stage);
-    HIPCHK(e);
-    if (n_stored) *n_stored = c[CTR_STORED];
-    if (n_duplicate) *n_duplicate = c[CTR_DUPLICATE];
-    if (n_zero) *n_zero = c[CTR_ZERO];
-    if (n_full) *n_full = c[CTR_FULL];
-    if (n_entries) *n_entries = c[CTR_ENTRIES];
-    if (c[CTR_STORED] + c[CTR_DUPLICATE] + c[CTR_ZERO] + c[CTR_FULL] != n)
-        return fail(BSGS_ERR_STATE, "distinguished-point table: %llu entries to load, %llu accounted for", (unsigned long long)n,
-                    (unsigned long long)(c[CTR_STORED] + c[CTR_DUPLICATE] + c[CTR_ZERO] + c[CTR_FULL]));
-    return BSGS_OK;
+    return rc;
 }
 
 extern "C" int bsgs_kangaroo_dptable_read(bsgs_dev *d, bsgs_kangaroo_dp_entry *entries, uint64_t max, uint64_t *n)
@@ -428,14 +324,14 @@ extern "C" int bsgs_kangaroo_dptable_read(bsgs_dev *d, bsgs_kangaroo_dp_entry *e
     if (int rc = dpt_herd(d, &k, true)) return rc;
     HIPCHK(hipSetDevice(d->id));
     uint64_t held = 0;
-    if (int rc = dpt_entries(d, k, &held)) return rc;
+    if (int rc = bsgs_kang_table_entries(d, &k->dpt, &held)) return rc;
     *n = held;
     if (!max && !entries) return BSGS_OK;                            // the count alone
     if (max < held) return fail(BSGS_ERR_ARG, "room for %llu entries, the table holds %llu", (unsigned long long)max, (unsigned long long)held);
     if (!held) return BSGS_OK;
     if (!entries) return fail(BSGS_ERR_ARG, "null");
     DptHarvestArgs H;
-    H.tag = k->dpt_tag; H.d = k->dpt_d; H.who = (const u32x2 *)k->dpt_who; H.out = nullptr; H.ctr = k->dpt_ctr; H.slots = k->dpt_slots; H.max = held;
+    H.tag = k->dpt.tag; H.d = k->dpt.d; H.who = k->dpt.who; H.out = nullptr; H.ctr = k->dpt.ctr; H.slots = k->dpt.slots; H.max = held;
     hipError_t e = hipMalloc(&H.out, (size_t)held * 32);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -443,26 +339,25 @@ extern "C" int bsgs_kangaroo_dptable_read(bsgs_dev *d, bsgs_kangaroo_dp_entry *e
                     (unsigned long long)(held * 32), hipGetErrorString(e));
     }
     uint64_t met = 0;
-    e = hipMemsetAsync(k->dpt_ctr + CTR_MET, 0, 8, d->stream);
+    e = hipMemsetAsync(k->dpt.ctr + CTR_MET, 0, 8, d->stream);
     if (e == hipSuccess) {
-        const u32 blocks = (u32)std::min<uint64_t>((k->dpt_slots + 255u) / 256u, DPT_SCAN_GRID_MAX);
+        const u32 blocks = (u32)std::min<uint64_t>((k->dpt.slots + 255u) / 256u, KT_SCAN_GRID_MAX);
         hipLaunchKernelGGL(kangaroo_dptable_harvest_kernel, dim3(blocks), dim3(256), 0, d->stream, H);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&met, k->dpt_ctr + CTR_MET, 8, hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&met, k->dpt.ctr + CTR_MET, 8, hipMemcpyDeviceToHost, d->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(entries, H.out, (size_t)held * 32, hipMemcpyDeviceToHost, d->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
     (void)hipFree(H.out);
     HIPCHK(e);
-    if (met != held) return fail(BSGS_ERR_STATE, "distinguished-point table: %llu occupied slots, %llu entries counted", (unsigned long long)met, (unsigned long long)held);
-    return BSGS_OK;
+    return bsgs_kang_table_met_check(met, held, "distinguished-point table");
 }
 
 extern "C" int bsgs_kangaroo_dptable_end(bsgs_dev *d)
 {
     if (!d) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = d->kangaroo;
-    if (!k || !k->dpt_tag) return BSGS_OK;
+    if (!k || !k->dpt.tag) return BSGS_OK;
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipStreamSynchronize(d->stream));
     dpt_free(k);

@@ -2,10 +2,9 @@
 // the device", the paragraphs "load" and "sorted read"; tests/kangaroo_tames_extend_model.py restates it): entries made earlier are loaded into the
 // growing table, and the finished table leaves the device sorted by tag and cut.  A unit of its own: the insert and the harvest of kangaroo_tames_gen.hip are
 // compiled as they were.
-//   load      (tag, d) pairs of the caller's, 24 bytes each, staged in chunks of TAMES_LOAD_CHUNK.  One pair per lane, a wave strides over the chunk.  The insert's
-//             rule and its coherence rule: old = atomicCAS(&tag[s], 0, t) from the home slot on, wrapping, at most `slots` times, and nothing but that return
-//             value decides what a slot holds.  Nothing is handed back: the four outcomes are counted, one vector atomic per wave and outcome (__ballot).
-//   sorted    harvest as kangaroo_tames_gen.hip's (ballot compaction, one atomic per wave), which also numbers the entries and folds the OR and the AND of all
+//   load      (tag, d) pairs of the caller's, 24 bytes each, staged in chunks of TAMES_LOAD_CHUNK.  One pair per lane, a wave strides over the chunk; each pair
+//             claims a slot by the table's rule (kangaroo_table.hip.h, with the coherence rule).  Nothing is handed back: the four outcomes are counted.
+//   sorted    harvest as kangaroo_tames_gen.hip's (the wave's reservation of kangaroo_table.hip.h), which also numbers the entries and folds the OR and the AND of all
 //   read      tags (one atomic each per wave); then an LSD radix sort of (tag, u32 number) by 8-bit digits.  A digit on which all tags agree -- a zero byte of
 //             OR ^ AND -- costs no pass.  A pass is three kernels, and no block waits for another inside one:
 //               hist     block b counts the digits of its tile of TAMES_SORT_TILE entries in LDS -> counts[digit][b]
@@ -13,29 +12,19 @@
 //               scatter  block b: where digit v of tile b starts = (totals of the digits below v) + counts[v][b]; its four waves own consecutive sub-tiles, a
 //                        wave takes 64 entries a round in order, lanes of equal digit find each other by eight ballots and rank by lane, so the pass is stable
 //             and one gather of the 16-byte d by number for the entries that cross the bus.  Every store is bounded by n.
-#include "bsgs_internal.h"
+#include "kangaroo_table.hip.h"
 
 #define TAMES_LOAD_CHUNK BSGS_KANGAROO_TAMES_LOAD_CHUNK   // pairs staged per kernel
-#define TAMES_LOAD_GRID_MAX 4096u
 #define TAMES_SORT_TILE BSGS_KANGAROO_TAMES_SORT_TILE     // entries per block and pass: 4 waves x TAMES_SORT_ROUNDS rounds x 64 lanes
 #define TAMES_SORT_ROUNDS 8u
-#define TAMES_SORT_HARVEST_GRID_MAX 4096u
 static_assert(TAMES_SORT_TILE == 4u * TAMES_SORT_ROUNDS * 64u, "a block's tile is four waves' sub-tiles");
-
-// gen_ctr (eight u64): [0] entries, [1] the harvest's count (kangaroo_tames_gen.hip), and here:
-#define CTR_STORED 2
-#define CTR_DUPLICATE 3
-#define CTR_ZERO 4
-#define CTR_FULL 5
-#define CTR_OR 6
-#define CTR_AND 7
 
 struct TamesLoadArgs {
     const u64 *in_tag;     // [n] the staged chunk
     const u32x4 *in_d;     // [n]
     u64 *tag;              // [slots]
     u32x4 *d;              // [slots]
-    u64 *ctr;              // gen_ctr
+    u64 *ctr;              // the table's counters
     u64 slot_mask;
     u32 n;
 };
@@ -49,25 +38,10 @@ __global__ void __launch_bounds__(256) kangaroo_tames_load_kernel(const TamesLoa
         u32 what = 0;                                                // 0: no pair in this lane; else CTR_*
         if (i < A.n) {
             const u64 tag = A.in_tag[i];
-            if (tag == 0ull) what = CTR_ZERO;
-            else {
-                what = CTR_FULL;
-                u64 s = (tag >> 6) & A.slot_mask;
-                for (u64 it = 0; it <= A.slot_mask; it++) {
-                    const u64 old = atomicCAS((unsigned long long *)&A.tag[s], 0ull, (unsigned long long)tag);      // the only way a tag is read
-                    if (old == 0ull) { A.d[s] = A.in_d[i]; what = CTR_STORED; break; }
-                    if (old == tag) { what = CTR_DUPLICATE; break; }
-                    s = (s + 1ull) & A.slot_mask;
-                }
-            }
+            u64 s;
+            what = tag == 0ull ? CTR_ZERO : kt_claim(A.tag, A.slot_mask, tag, s, [&](u64 at) { A.d[at] = A.in_d[i]; });
         }
-        for (u32 k = CTR_STORED; k <= CTR_FULL; k++) {
-            const u64 m = __ballot(what == k);
-            if (m && (int)lane == __builtin_ctzll(m)) {
-                atomicAdd((unsigned long long *)&A.ctr[k], (unsigned long long)__builtin_popcountll(m));
-                if (k == CTR_STORED) atomicAdd((unsigned long long *)&A.ctr[0], (unsigned long long)__builtin_popcountll(m));
-            }
-        }
+        kt_count_outcomes(A.ctr, what, lane);
     }
 }
 
@@ -77,7 +51,7 @@ struct TamesSortHarvestArgs {
     u64 *out_tag;          // [max]
     u32 *out_idx;          // [max] the entry's number: where its d lies in out_d
     u32x4 *out_d;          // [max]
-    u64 *ctr;              // gen_ctr: [1] occupied slots met (zeroed by the caller), [6] OR of the tags (0), [7] AND of the tags (all ones)
+    u64 *ctr;              // the table's counters: CTR_MET (zeroed by the caller), CTR_OR of the tags (0), CTR_AND of the tags (all ones)
     u64 slots, max;
 };
 
@@ -92,18 +66,11 @@ __global__ void __launch_bounds__(256) kangaroo_tames_sort_harvest_kernel(const 
         const u64 t = s < A.slots ? A.tag[s] : 0ull;
         const bool occ = t != 0ull;
         if (occ) { any |= t; all &= t; }
-        const u64 m = __ballot(occ);
-        if (m) {
-            u64 pos0 = 0;
-            const int leader = __builtin_ctzll(m);
-            if ((int)lane == leader) pos0 = atomicAdd((unsigned long long *)&A.ctr[1], (unsigned long long)__builtin_popcountll(m));
-            pos0 = __shfl(pos0, leader);
-            const u64 pos = pos0 + (u64)__builtin_popcountll(m & ((1ull << lane) - 1));
-            if (occ && pos < A.max) {                                // the bound of every store
-                A.out_tag[pos] = t;
-                A.out_idx[pos] = (u32)pos;
-                A.out_d[pos] = A.d[s];
-            }
+        const u64 pos = kt_reserve(occ, lane, &A.ctr[CTR_MET], 0);
+        if (occ && pos < A.max) {                                    // the bound of every store
+            A.out_tag[pos] = t;
+            A.out_idx[pos] = (u32)pos;
+            A.out_d[pos] = A.d[s];
         }
     }
     for (int o = 32; o; o >>= 1) {                                   // the wave's OR and AND, then one atomic each
@@ -249,16 +216,6 @@ __global__ void __launch_bounds__(256) kangaroo_tames_sort_gather_kernel(const T
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------
-static int tames_extend_herd(bsgs_dev *d, bsgs_kangaroo **k)
-{
-    if (!d) return fail(BSGS_ERR_ARG, "null");
-    *k = d->kangaroo;
-    if (!*k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
-    if ((*k)->key) return fail(BSGS_ERR_STATE, "a tame table grows under the herds of bsgs_kangaroo_setup and bsgs_kangaroo_setup_sym");
-    if (!(*k)->gen_tag) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_tames_gen_begin first");
-    return BSGS_OK;
-}
-
 static void free_all(std::initializer_list<void *> ps) { for (void *p : ps) if (p) (void)hipFree(p); }
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
@@ -266,13 +223,13 @@ extern "C" int bsgs_kangaroo_tames_gen_load(bsgs_dev *d, const uint64_t *x_lo64,
                                             uint64_t *n_full, uint64_t *n_entries)
 {
     bsgs_kangaroo *k = nullptr;
-    if (int rc = tames_extend_herd(d, &k)) return rc;
+    if (int rc = bsgs_kangaroo_tames_gen_herd(d, &k, true)) return rc;
     if (n && (!x_lo64 || !d_le)) return fail(BSGS_ERR_ARG, "null");
-    if (n > (1ull << 31)) return fail(BSGS_ERR_ARG, "loading %llu entries: at most 2^31", (unsigned long long)n);
+    if (n > KT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "loading %llu entries: at most 2^31", (unsigned long long)n);
     HIPCHK(hipSetDevice(d->id));
     const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), TAMES_LOAD_CHUNK);
     TamesLoadArgs A;
-    A.in_tag = nullptr; A.in_d = nullptr; A.tag = k->gen_tag; A.d = k->gen_d; A.ctr = k->gen_ctr; A.slot_mask = k->gen_slots - 1; A.n = 0;
+    A.in_tag = nullptr; A.in_d = nullptr; A.tag = k->gen.tag; A.d = k->gen.d; A.ctr = k->gen.ctr; A.slot_mask = k->gen.slots - 1; A.n = 0;
     hipError_t e = hipMalloc((void **)&A.in_tag, (size_t)chunk * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&A.in_d, (size_t)chunk * 16);
     if (e != hipSuccess) {
@@ -281,42 +238,31 @@ extern "C" int bsgs_kangaroo_tames_gen_load(bsgs_dev *d, const uint64_t *x_lo64,
         return fail(BSGS_ERR_NOMEM, "loading into a growing tame table: a chunk of %llu entries needs %llu bytes of tags and %llu of offsets (%s)", (unsigned long long)chunk,
                     (unsigned long long)(chunk * 8), (unsigned long long)(chunk * 16), hipGetErrorString(e));
     }
-    uint64_t ctr[8] = {0};
-    e = hipMemsetAsync(k->gen_ctr + CTR_STORED, 0, 4 * 8, d->stream);
+    e = hipMemsetAsync(k->gen.ctr + CTR_STORED, 0, 4 * 8, d->stream);
     for (uint64_t pos = 0; pos < n && e == hipSuccess; pos += chunk) {
         const uint32_t m = (uint32_t)std::min(chunk, n - pos);
         e = hipMemcpyAsync((void *)A.in_tag, x_lo64 + pos, (size_t)m * 8, hipMemcpyHostToDevice, d->stream);
         if (e == hipSuccess) e = hipMemcpyAsync((void *)A.in_d, d_le + 16 * pos, (size_t)m * 16, hipMemcpyHostToDevice, d->stream);
         if (e != hipSuccess) break;
         A.n = m;
-        const u32 blocks = std::min((m + 255u) / 256u, TAMES_LOAD_GRID_MAX);
+        const u32 blocks = std::min((m + 255u) / 256u, KT_SCAN_GRID_MAX);
         hipLaunchKernelGGL(kangaroo_tames_load_kernel, dim3(blocks), dim3(256), 0, d->stream, A);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(ctr, k->gen_ctr, sizeof ctr, hipMemcpyDeviceToHost, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    const int rc = bsgs_kang_table_loaded(d, &k->gen, e, n, n_stored, n_duplicate, n_zero, n_full, n_entries,
+                                          "loading into a growing tame table: %llu pairs, %llu accounted for");
     free_all({(void *)A.in_tag, (void *)A.in_d});
-    HIPCHK(e);
-    if (n_stored) *n_stored = ctr[CTR_STORED];
-    if (n_duplicate) *n_duplicate = ctr[CTR_DUPLICATE];
-    if (n_zero) *n_zero = ctr[CTR_ZERO];
-    if (n_full) *n_full = ctr[CTR_FULL];
-    if (n_entries) *n_entries = ctr[0];
-    if (ctr[CTR_STORED] + ctr[CTR_DUPLICATE] + ctr[CTR_ZERO] + ctr[CTR_FULL] != n)
-        return fail(BSGS_ERR_STATE, "loading into a growing tame table: %llu pairs, %llu accounted for", (unsigned long long)n,
-                    (unsigned long long)(ctr[CTR_STORED] + ctr[CTR_DUPLICATE] + ctr[CTR_ZERO] + ctr[CTR_FULL]));
-    return BSGS_OK;
+    return rc;
 }
 
 extern "C" int bsgs_kangaroo_tames_gen_read_sorted(bsgs_dev *d, uint64_t *x_lo64, uint8_t *d_le, uint64_t max, uint64_t *n)
 {
     if (!n) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
-    if (int rc = tames_extend_herd(d, &k)) return rc;
+    if (int rc = bsgs_kangaroo_tames_gen_herd(d, &k, true)) return rc;
     HIPCHK(hipSetDevice(d->id));
     uint64_t entries = 0;
-    HIPCHK(hipMemcpyAsync(&entries, k->gen_ctr, 8, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
+    if (int rc = bsgs_kang_table_entries(d, &k->gen, &entries)) return rc;
     *n = entries;
     const uint64_t m = std::min(entries, max);
     if (!m) return BSGS_OK;
@@ -344,22 +290,22 @@ extern "C" int bsgs_kangaroo_tames_gen_read_sorted(bsgs_dev *d, uint64_t *x_lo64
                     (unsigned long long)(b_counts + 1024), hipGetErrorString(e));
     }
     uint64_t got[3] = {0, 0, 0};                                     // occupied slots met, OR, AND
-    e = hipMemsetAsync(k->gen_ctr + 1, 0, 8, d->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(k->gen_ctr + CTR_OR, 0, 8, d->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(k->gen_ctr + CTR_AND, 0xFF, 8, d->stream);
+    e = hipMemsetAsync(k->gen.ctr + CTR_MET, 0, 8, d->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(k->gen.ctr + CTR_OR, 0, 8, d->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(k->gen.ctr + CTR_AND, 0xFF, 8, d->stream);
     if (e == hipSuccess) {
         TamesSortHarvestArgs H;
-        H.tag = k->gen_tag; H.d = k->gen_d; H.out_tag = key[0]; H.out_idx = val[0]; H.out_d = dh; H.ctr = k->gen_ctr; H.slots = k->gen_slots; H.max = entries;
-        const u32 blocks = (u32)std::min<uint64_t>((k->gen_slots + 255u) / 256u, TAMES_SORT_HARVEST_GRID_MAX);
+        H.tag = k->gen.tag; H.d = k->gen.d; H.out_tag = key[0]; H.out_idx = val[0]; H.out_d = dh; H.ctr = k->gen.ctr; H.slots = k->gen.slots; H.max = entries;
+        const u32 blocks = (u32)std::min<uint64_t>((k->gen.slots + 255u) / 256u, KT_SCAN_GRID_MAX);
         hipLaunchKernelGGL(kangaroo_tames_sort_harvest_kernel, dim3(blocks), dim3(256), 0, d->stream, H);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&got[0], k->gen_ctr + 1, 8, hipMemcpyDeviceToHost, d->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&got[1], k->gen_ctr + CTR_OR, 16, hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&got[0], k->gen.ctr + CTR_MET, 8, hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&got[1], k->gen.ctr + CTR_OR, 16, hipMemcpyDeviceToHost, d->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
     if (e == hipSuccess && got[0] != entries) {
         release();
-        return fail(BSGS_ERR_STATE, "growing tame table: %llu occupied slots, %llu entries counted", (unsigned long long)got[0], (unsigned long long)entries);
+        return bsgs_kang_table_met_check(got[0], entries, "growing tame table");
     }
     int cur = 0;
     const uint64_t differ = got[1] ^ got[2];                         // the bits on which not all tags agree
@@ -377,7 +323,7 @@ extern "C" int bsgs_kangaroo_tames_gen_read_sorted(bsgs_dev *d, uint64_t *x_lo64
     if (e == hipSuccess) {
         TamesSortGatherArgs G;
         G.idx = val[cur]; G.d = dh; G.out_d = ds; G.m = (u32)m; G.n = (u32)entries;
-        const u32 blocks = (u32)std::min<uint64_t>((m + 255u) / 256u, TAMES_SORT_HARVEST_GRID_MAX);
+        const u32 blocks = (u32)std::min<uint64_t>((m + 255u) / 256u, KT_SCAN_GRID_MAX);
         hipLaunchKernelGGL(kangaroo_tames_sort_gather_kernel, dim3(blocks), dim3(256), 0, d->stream, G);
         e = hipGetLastError();
     }

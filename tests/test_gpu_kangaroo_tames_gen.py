@@ -221,7 +221,9 @@ def test_states(jump_table):
         for capacity in (0, (1 << 31) + 1):
             with pytest.raises(pybsgs.BsgsError, match="error -1: .*1..2\\^31"):
                 d.kangaroo_tames_gen_begin(capacity)
-        d.kangaroo_tames_gen_begin(64)
+            with pytest.raises(pybsgs.BsgsError, match="error -3: bsgs_kangaroo_tames_gen_begin first"):      # a begin that is refused leaves no table
+                d.kangaroo_run_tames_gen(1)
+        d.kangaroo_tames_gen_begin(64)                                # and a good one after it works
         with pytest.raises(pybsgs.BsgsError, match="error -1: .*record capacity"):
             d.kangaroo_tames_gen_insert([(k + 1, 1, 0) for k in range(65)])
         back, n = d.kangaroo_tames_gen_insert([(5, 1, 0), (6, 2, 0), (5, 3, 0)])

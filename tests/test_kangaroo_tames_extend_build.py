@@ -13,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = {"bsgs_kangaroo_tames_gen_load", "bsgs_kangaroo_tames_gen_read_sorted"}
 # kernel -> (VGPRs, SGPRs, LDS bytes per block) as hipcc -O3 --offload-arch=gfx950 reports them
 KERNELS = {
-    "kangaroo_tames_load_kernel(TamesLoadArgs)": (20, 36, 0),
-    "kangaroo_tames_sort_harvest_kernel(TamesSortHarvestArgs)": (28, 38, 0),
+    "kangaroo_tames_load_kernel(TamesLoadArgs)": (18, 36, 0),
+    "kangaroo_tames_sort_harvest_kernel(TamesSortHarvestArgs)": (26, 38, 0),
     "kangaroo_tames_sort_hist_kernel(TamesSortArgs)": (8, 22, 1024),
     "kangaroo_tames_sort_scan_kernel(TamesSortArgs)": (21, 36, 16),
     "kangaroo_tames_sort_scatter_kernel(TamesSortArgs)": (62, 38, 5136),
