@@ -740,12 +740,30 @@ class Device:
         return [(int.from_bytes(bytes(s.x), "little"), int.from_bytes(bytes(s.y), "little"), int.from_bytes(bytes(s.d), "little"), s.flags) +
                 ((s.reserved[0],) if keyed else ()) + ((tuple(s.reserved),) if reserved else ()) for s in arr]
 
-    def kangaroo_run(self, steps):
+    # raw=True on the calls below: records cross as the bytes of 64-byte bsgs_kangaroo_record, without one Python object per record
+    @staticmethod
+    def _raw_records_in(records):
+        """the bytes of m records (anything with the buffer protocol) -> (a pointer the C-ABI takes, m, the object that keeps the bytes alive)"""
+        b = records if isinstance(records, bytes) else bytes(records)
+        if len(b) % 64:
+            raise BsgsError("raw records: %d bytes are no multiple of 64" % len(b))
+        return C.cast(C.c_char_p(b), C.POINTER(KangarooRecord)), len(b) // 64, b
+
+    @staticmethod
+    def _raw_records_out(cap):
+        buf = C.create_string_buffer(64 * max(1, cap))
+        return C.cast(buf, C.POINTER(KangarooRecord)), buf
+
+    def kangaroo_run(self, steps, raw=False):
         """one launch of `steps` steps: (records, dropped, kernel ms); a record is {x, d (mod 2^128), kangaroo, flags, step, key}, key = the key of
-        the kangaroo in a herd of kangaroo_setup_sym_keys and 0 in every other"""
+        the kangaroo in a herd of kangaroo_setup_sym_keys and 0 in every other; raw: the bytes of the records in the place of the list"""
         cap = self._kang_cap
-        recs = (KangarooRecord * cap)()
         n, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_float()
+        if raw:
+            recs, buf = self._raw_records_out(cap)
+            _chk(self.L.bsgs_kangaroo_run(self.h, steps, recs, cap, C.byref(n), C.byref(dropped), C.byref(ms)))
+            return buf.raw[:64 * n.value], dropped.value, ms.value
+        recs = (KangarooRecord * cap)()
         _chk(self.L.bsgs_kangaroo_run(self.h, steps, recs, cap, C.byref(n), C.byref(dropped), C.byref(ms)))
         out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step, "key": r.reserved}
                for r in recs[:n.value]]
@@ -756,13 +774,17 @@ class Device:
         as long as the herd (kangaroo_setup, kangaroo_setup_sym)"""
         _chk(self.L.bsgs_kangaroo_tames_install(self.h, (C.c_uint64 * max(1, len(tags)))(*tags), len(tags)))
 
-    def kangaroo_run_tames(self, steps):
+    def kangaroo_run_tames(self, steps, raw=False):
         """one launch of `steps` steps matched against the tame table on the device: (records, n_seen, dropped, kernel ms).  Only the records whose x is in
         the table and the DEAD ones come back, as kangaroo_run's plus "entry": the table entry's number, None for a DEAD record that matched nothing;
-        n_seen = the records the walk produced"""
+        n_seen = the records the walk produced; raw: the bytes of the records (`reserved` = entry number + 1, 0 for None) in the place of the list"""
         cap = max(1, self._kang_cap)
-        recs = (KangarooRecord * cap)()
         n, seen, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_float()
+        if raw:
+            recs, buf = self._raw_records_out(cap)
+            _chk(self.L.bsgs_kangaroo_run_tames(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(dropped), C.byref(ms)))
+            return buf.raw[:64 * n.value], seen.value, dropped.value, ms.value
+        recs = (KangarooRecord * cap)()
         _chk(self.L.bsgs_kangaroo_run_tames(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(dropped), C.byref(ms)))
         out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
                 "entry": r.reserved - 1 if r.reserved else None} for r in recs[:n.value]]
@@ -772,12 +794,18 @@ class Device:
         """kangaroo_tames_install for the herd of kangaroo_setup_sym_keys, whose records keep their key"""
         _chk(self.L.bsgs_kangaroo_tames_install_keys(self.h, (C.c_uint64 * max(1, len(tags)))(*tags), len(tags)))
 
-    def kangaroo_run_tames_keys(self, steps, max_recs=None):
+    def kangaroo_run_tames_keys(self, steps, max_recs=None, raw=False):
         """kangaroo_run_tames for the herd of kangaroo_setup_sym_keys: every record also has "key" (the word the walk wrote), and "entry" comes from the
-        parallel array (entry number, None for a DEAD record that matched nothing); max_recs: a host buffer smaller than the record capacity"""
+        parallel array (entry number, None for a DEAD record that matched nothing); max_recs: a host buffer smaller than the record capacity; raw: (the
+        bytes of the records, the bytes of their u32 entry words: entry number + 1, 0 for None) in the place of the list"""
         cap = max(1, self._kang_cap if max_recs is None else max_recs)
-        recs, ent = (KangarooRecord * cap)(), (C.c_uint32 * cap)()
         n, seen, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_float()
+        if raw:
+            recs, buf = self._raw_records_out(cap)
+            ent = (C.c_uint32 * cap)()
+            _chk(self.L.bsgs_kangaroo_run_tames_keys(self.h, steps, recs, ent, cap, C.byref(n), C.byref(seen), C.byref(dropped), C.byref(ms)))
+            return (buf.raw[:64 * n.value], bytes(ent)[:4 * n.value]), seen.value, dropped.value, ms.value
+        recs, ent = (KangarooRecord * cap)(), (C.c_uint32 * cap)()
         _chk(self.L.bsgs_kangaroo_run_tames_keys(self.h, steps, recs, ent, cap, C.byref(n), C.byref(seen), C.byref(dropped), C.byref(ms)))
         out = [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
                 "key": r.reserved, "entry": e - 1 if e else None} for r, e in zip(recs[:n.value], ent[:n.value])]
@@ -793,17 +821,29 @@ class Device:
         return [{"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
                  "reason": r.reserved} for r in recs[:n]]
 
-    def kangaroo_run_tames_gen(self, steps, max_recs=None):
+    def kangaroo_run_tames_gen(self, steps, max_recs=None, raw=False):
         """one launch of `steps` steps inserted into the growing table on the device: (handed-back records, n_seen, n_entries, dropped, kernel ms); a
-        handed-back record is kangaroo_run's with "reason" (KANGAROO_GEN_*) in the place of "key" """
+        handed-back record is kangaroo_run's with "reason" (KANGAROO_GEN_*) in the place of "key"; raw: their bytes (the reason in `reserved`) """
         cap = max(1, self._kang_cap if max_recs is None else max_recs)
-        recs = (KangarooRecord * cap)()
         n, seen, entries, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        if raw:
+            recs, buf = self._raw_records_out(cap)
+            _chk(self.L.bsgs_kangaroo_run_tames_gen(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
+            return buf.raw[:64 * n.value], seen.value, entries.value, dropped.value, ms.value
+        recs = (KangarooRecord * cap)()
         _chk(self.L.bsgs_kangaroo_run_tames_gen(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
         return self._gen_handed_back(recs, n.value), seen.value, entries.value, dropped.value, ms.value
 
-    def kangaroo_tames_gen_insert(self, records):
-        """the insert alone on records of the caller's, (tag or x, d, flags[, kangaroo]) each: (handed-back records, n_entries)"""
+    def kangaroo_tames_gen_insert(self, records, raw=False):
+        """the insert alone on records of the caller's, (tag or x, d, flags[, kangaroo]) each: (handed-back records, n_entries); raw: records = the bytes
+        of 64-byte records, inserted as they are, and the handed-back ones come as bytes too (the reason in `reserved`)"""
+        if raw:
+            arr, m, keep = self._raw_records_in(records)
+            cap = max(1, self._kang_cap)
+            out, buf = self._raw_records_out(cap)
+            n, entries = C.c_uint32(), C.c_uint64()
+            _chk(self.L.bsgs_kangaroo_tames_gen_insert(self.h, arr, m, out, cap, C.byref(n), C.byref(entries)))
+            return buf.raw[:64 * n.value], entries.value
         m = len(records)
         arr = (KangarooRecord * max(1, m))()
         for k, (x, d, fl, *kang) in enumerate(records):
@@ -817,19 +857,22 @@ class Device:
         _chk(self.L.bsgs_kangaroo_tames_gen_insert(self.h, arr, m, out, cap, C.byref(n), C.byref(entries)))
         return self._gen_handed_back(out, n.value), entries.value
 
-    def kangaroo_tames_gen_read(self, max_entries=None):
-        """the table's entries as a list of (tag, d mod 2^128), in any order; max_entries: the room offered (None: what the table holds)"""
+    def kangaroo_tames_gen_read(self, max_entries=None, raw=False):
+        """the table's entries as a list of (tag, d mod 2^128), in any order; max_entries: the room offered (None: what the table holds); raw: (the tags
+        as the bytes of little-endian u64, the offsets as bytes) in the place of the list"""
         n = C.c_uint64()
         if max_entries is None:
             rc = self.L.bsgs_kangaroo_tames_gen_read(self.h, None, None, 0, C.byref(n))
             if n.value == 0:
                 _chk(rc)
-                return []
+                return (b"", b"") if raw else []
             max_entries = n.value
         tags, d = (C.c_uint64 * max(1, max_entries))(), C.create_string_buffer(16 * max(1, max_entries))
         _chk(self.L.bsgs_kangaroo_tames_gen_read(self.h, tags, d, max_entries, C.byref(n)))
-        raw = d.raw
-        return [(tags[k], int.from_bytes(raw[16 * k:16 * k + 16], "little")) for k in range(n.value)]
+        db = d.raw
+        if raw:
+            return bytes(tags)[:8 * n.value], db[:16 * n.value]
+        return [(tags[k], int.from_bytes(db[16 * k:16 * k + 16], "little")) for k in range(n.value)]
 
     def kangaroo_tames_gen_end(self):
         _chk(self.L.bsgs_kangaroo_tames_gen_end(self.h))
@@ -864,18 +907,31 @@ class Device:
         """allocates the table for `capacity` entries under the herd of kangaroo_setup / kangaroo_setup_sym; replaces an earlier one"""
         _chk(self.L.bsgs_kangaroo_dptable_begin(self.h, capacity))
 
-    def kangaroo_run_dptable(self, steps, max_recs=None):
+    def kangaroo_run_dptable(self, steps, max_recs=None, raw=False):
         """one launch of `steps` steps inserted into the table on the device: (hand-backs, n_seen, n_entries, dropped, kernel ms); a hand-back is
         kangaroo_run's record with "reason" (KANGAROO_DPT_*) in the place of "key", and a duplicate is two of them: the stored entry (reason
-        KANGAROO_DPT_STORED, x = its tag, flags = its type), then the walk's record; max_recs: a host buffer of another size than two per record"""
+        KANGAROO_DPT_STORED, x = its tag, flags = its type), then the walk's record; max_recs: a host buffer of another size than two per record; raw: the
+        bytes of the hand-backs (the reason in `reserved`) in the place of the list"""
         cap = 2 * self._kang_cap if max_recs is None else max_recs
-        recs = (KangarooRecord * max(1, cap))()
         n, seen, entries, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        if raw:
+            recs, buf = self._raw_records_out(cap)
+            _chk(self.L.bsgs_kangaroo_run_dptable(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
+            return buf.raw[:64 * n.value], seen.value, entries.value, dropped.value, ms.value
+        recs = (KangarooRecord * max(1, cap))()
         _chk(self.L.bsgs_kangaroo_run_dptable(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
         return self._gen_handed_back(recs, n.value), seen.value, entries.value, dropped.value, ms.value
 
-    def kangaroo_dptable_insert(self, records, max_recs=None):
-        """insert and resolve alone on records of the caller's, (tag or x, d, flags[, kangaroo]) each: (hand-backs, n_entries, dropped)"""
+    def kangaroo_dptable_insert(self, records, max_recs=None, raw=False):
+        """insert and resolve alone on records of the caller's, (tag or x, d, flags[, kangaroo]) each: (hand-backs, n_entries, dropped); raw: records = the
+        bytes of 64-byte records, inserted as they are, and the hand-backs come as bytes too (the reason in `reserved`)"""
+        if raw:
+            arr, m, keep = self._raw_records_in(records)
+            cap = 2 * self._kang_cap if max_recs is None else max_recs
+            out, buf = self._raw_records_out(cap)
+            n, entries, dropped = C.c_uint32(), C.c_uint64(), C.c_uint64()
+            _chk(self.L.bsgs_kangaroo_dptable_insert(self.h, arr, m, out, cap, C.byref(n), C.byref(entries), C.byref(dropped)))
+            return buf.raw[:64 * n.value], entries.value, dropped.value
         m = len(records)
         arr = (KangarooRecord * max(1, m))()
         for k, (x, d, fl, *kang) in enumerate(records):
