@@ -19,7 +19,7 @@ int bsgs_fail(int code, const char *fmt, ...);
 // kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table, the staging of a seed call and the key list;
 // kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records;
 // kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer; kangaroo_tames_extend.hip: its load and sorted read;
-// kangaroo_dptable.hip: the distinguished-point table of a search with its own buffer of hand-backs (both tables: KangTable)
+// kangaroo_dptable.hip: the distinguished-point table of a search with its own buffer of hand-backs (both tables: KangTable); kangaroo_dptable_keys.hip: its insert for a key list
 // the table in device memory (kangaroo_table.hip.h has the rule): tag[slots] (0 = empty), the offset of each, its owner (kangaroo, type; null for the tame
 // table), eight counters.  It exists where tag is set; slots is a power of two
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
@@ -55,6 +55,7 @@ struct bsgs_kangaroo {
     KangTable gen;                         // bsgs_kangaroo_tames_gen_begin: the tame table that grows during generation (no owners)
     KangTable dpt;                         // bsgs_kangaroo_dptable_begin: the distinguished-point table of a search
     u32 *dpt_out = nullptr;                // its hand-backs of a launch: u64 places taken, u64 records handed back | 2 * cap records from byte 64
+    bool dpt_keyed = false;                // bsgs_kangaroo_dptable_begin_keys: who[s].y is the work file's owner word (0 tame, 1 + key, bit 31 NEG), not a type
 };
 
 struct bsgs_dev {
@@ -228,6 +229,17 @@ int bsgs_kang_table_loaded(bsgs_dev *d, const KangTable *t, hipError_t e, uint64
                            uint64_t *n_entries, const char *text);
 // behind a harvest (its caller has zeroed ctr[CTR_MET] before it): what it met against the entries counted (`what`: the table's name in the error)
 int bsgs_kang_table_met_check(uint64_t met, uint64_t entries, const char *what);
+// kangaroo_dptable.hip: the host side of the distinguished-point table, shared with kangaroo_dptable_keys.hip (the table for a key list).  `keyed`: the calls
+// of that unit; a table begun one way refuses the run and the insert of the other (BSGS_ERR_STATE), load, read and end serve both
+int bsgs_kang_dpt_begin(bsgs_dev *d, uint64_t capacity, bool keyed);
+int bsgs_kang_dpt_run(bsgs_dev *d, bool keyed, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen, uint64_t *n_entries,
+                      uint64_t *dropped, float *kernel_ms);
+int bsgs_kang_dpt_insert(bsgs_dev *d, bool keyed, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs, uint32_t *nrecs,
+                         uint64_t *n_entries, uint64_t *dropped);
+int bsgs_kang_dpt_resolve(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blocks);      // the resolve kernel behind an insert, on the stream
+static inline uint32_t bsgs_kang_dpt_out_cap(const bsgs_kangaroo *k) { return 2u * k->cap; }      // every record of a launch a duplicate: two places each (cap <= 2^26)
+// kangaroo_dptable_keys.hip: the keyed insert of the records in k->rec (their count at its head) on the stream
+int bsgs_kang_dpt_insert_keys_launch(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blocks);
 // hand a finished "lines + overflow list" table to the engine (it becomes the owner of both buffers)
 int bsgs_install_lines(bsgs_dev *d, u32x4 *lines, int lplog, u64 *ovf, uint64_t ovf_n, uint64_t ht_items, uint64_t w,
                        uint64_t overflow_buckets);

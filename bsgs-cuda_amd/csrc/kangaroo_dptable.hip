@@ -11,6 +11,8 @@
 //   equal tags in one launch: every one but the stored one comes back paired with it.
 //   load      32-byte entries of the caller's by the same rule, staged in chunks; the four outcomes are counted, nothing else comes back.
 //   harvest   strides over the slots and compacts the occupied ones into 32-byte entries, in any order.
+// The table for a key list (kangaroo_dptable_keys.hip) is this table with the work file's owner word where the type stands: its insert is that unit's kernel,
+// and resolve, load and harvest -- which copy who[s].y as it is -- and the host side below serve both.
 #include "kangaroo_table.hip.h"
 
 #define DPT_LOAD_CHUNK BSGS_KANGAROO_DPT_LOAD_CHUNK
@@ -166,22 +168,37 @@ static void dpt_free(bsgs_kangaroo *k)
     bsgs_kang_table_free(&k->dpt);
     if (k->dpt_out) (void)hipFree(k->dpt_out);
     k->dpt_out = nullptr;
+    k->dpt_keyed = false;
 }
 
-static inline uint32_t dpt_out_cap(const bsgs_kangaroo *k) { return 2u * k->cap; }      // every record of a launch a duplicate: two places each (cap <= 2^26)
+static inline uint32_t dpt_out_cap(const bsgs_kangaroo *k) { return bsgs_kang_dpt_out_cap(k); }
 
-// insert and resolve of the records in k->rec (their count at its head) on the stream
-static int dpt_insert(bsgs_dev *d, bsgs_kangaroo *k)
+static DptArgs dpt_args(const bsgs_kangaroo *k)
 {
     DptArgs A;
     A.rec = k->rec; A.tag = k->dpt.tag; A.d = k->dpt.d; A.who = k->dpt.who; A.out = k->dpt_out; A.ctr = k->dpt.ctr; A.slot_mask = k->dpt.slots - 1;
     A.cap = k->cap; A.out_cap = dpt_out_cap(k);
-    const u32 blocks = std::min((k->cap + 255u) / 256u, KT_INSERT_GRID_MAX);
-    hipLaunchKernelGGL(kangaroo_dptable_insert_kernel, dim3(blocks), dim3(256), 0, d->stream, A);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(kangaroo_dptable_resolve_kernel, dim3(blocks), dim3(256), 0, d->stream, A);
+    return A;
+}
+
+int bsgs_kang_dpt_resolve(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blocks)
+{
+    hipLaunchKernelGGL(kangaroo_dptable_resolve_kernel, dim3(blocks), dim3(256), 0, d->stream, dpt_args(k));
     HIPCHK(hipGetLastError());
     return BSGS_OK;
+}
+
+// insert and resolve of the records in k->rec (their count at its head) on the stream; a keyed table takes the insert of kangaroo_dptable_keys.hip
+static int dpt_insert(bsgs_dev *d, bsgs_kangaroo *k)
+{
+    const u32 blocks = std::min((k->cap + 255u) / 256u, KT_INSERT_GRID_MAX);
+    if (k->dpt_keyed) {
+        if (int rc = bsgs_kang_dpt_insert_keys_launch(d, k, blocks)) return rc;
+    } else {
+        hipLaunchKernelGGL(kangaroo_dptable_insert_kernel, dim3(blocks), dim3(256), 0, d->stream, dpt_args(k));
+        HIPCHK(hipGetLastError());
+    }
+    return bsgs_kang_dpt_resolve(d, k, blocks);
 }
 
 // the hand-backs of the launch that has finished -> recs, through the herd's pinned buffer in pieces of its size.  A pair is never split: when the cut at
@@ -203,17 +220,36 @@ static int dpt_copy_out(bsgs_dev *d, bsgs_kangaroo *k, uint64_t places, bsgs_kan
     return BSGS_OK;
 }
 
-static int dpt_herd(bsgs_dev *d, bsgs_kangaroo **k, bool table)
+// `table`: the call needs one; `want`: DPT_EITHER, or the kind of table the call is for.  A keyed table stands under a herd with a key list, that of
+// bsgs_kangaroo_setup_sym_keys included, which every other table call refuses.
+enum { DPT_EITHER = -1, DPT_UNKEYED = 0, DPT_KEYED = 1 };
+static int dpt_herd(bsgs_dev *d, bsgs_kangaroo **k, bool table, int want = DPT_UNKEYED)
 {
+    if (d && d->kangaroo && d->kangaroo->dpt.tag && d->kangaroo->dpt_keyed && table) {
+        *k = d->kangaroo;
+        if (want == DPT_UNKEYED)
+            return fail(BSGS_ERR_STATE, "the table was begun by bsgs_kangaroo_dptable_begin_keys: bsgs_kangaroo_run_dptable_keys and bsgs_kangaroo_dptable_insert_keys fill it");
+        return BSGS_OK;
+    }
+    if (want == DPT_KEYED) {
+        if (!d) return fail(BSGS_ERR_ARG, "null");
+        *k = d->kangaroo;
+        if (!*k) return fail(BSGS_ERR_STATE, "bsgs_kangaroo_setup first");
+        if (!(*k)->keys || !(*k)->n_keys)
+            return fail(BSGS_ERR_STATE, "a distinguished-point table for a key list serves the herds of bsgs_kangaroo_setup and bsgs_kangaroo_setup_sym_keys after bsgs_kangaroo_set_keys");
+        if (table) return fail(BSGS_ERR_STATE, (*k)->dpt.tag ? "the table was begun by bsgs_kangaroo_dptable_begin: bsgs_kangaroo_run_dptable and bsgs_kangaroo_dptable_insert fill it"
+                                                              : "bsgs_kangaroo_dptable_begin_keys first");
+        return BSGS_OK;
+    }
     return bsgs_kang_table_herd(d, k, &bsgs_kangaroo::dpt, "a distinguished-point table serves the herds of bsgs_kangaroo_setup and bsgs_kangaroo_setup_sym",
                                 table ? "bsgs_kangaroo_dptable_begin first" : nullptr);
 }
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
-extern "C" int bsgs_kangaroo_dptable_begin(bsgs_dev *d, uint64_t capacity)
+int bsgs_kang_dpt_begin(bsgs_dev *d, uint64_t capacity, bool keyed)
 {
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, false)) return rc;
+    if (int rc = dpt_herd(d, &k, false, keyed ? DPT_KEYED : DPT_UNKEYED)) return rc;
     if (!capacity || capacity > KT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "distinguished-point table of %llu entries: 1..2^31", (unsigned long long)capacity);
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -228,15 +264,18 @@ extern "C" int bsgs_kangaroo_dptable_begin(bsgs_dev *d, uint64_t capacity)
                     (unsigned long long)capacity, (unsigned long long)slots, (unsigned long long)(slots * 8), (unsigned long long)(slots * 16), (unsigned long long)(slots * 8),
                     (unsigned long long)out_bytes, hipGetErrorString(e));
     HIPCHK(e);
+    k->dpt_keyed = keyed;
     return BSGS_OK;
 }
 
-extern "C" int bsgs_kangaroo_run_dptable(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen,
-                                         uint64_t *n_entries, uint64_t *dropped, float *kernel_ms)
+extern "C" int bsgs_kangaroo_dptable_begin(bsgs_dev *d, uint64_t capacity) { return bsgs_kang_dpt_begin(d, capacity, false); }
+
+int bsgs_kang_dpt_run(bsgs_dev *d, bool keyed, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen, uint64_t *n_entries,
+                      uint64_t *dropped, float *kernel_ms)
 {
     if (!d || !nrecs) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, true)) return rc;
+    if (int rc = dpt_herd(d, &k, true, keyed ? DPT_KEYED : DPT_UNKEYED)) return rc;
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipMemsetAsync(k->dpt_out, 0, KANG_REC_HEADER, d->stream));
     if (int rc = bsgs_kangaroo_launch(d, steps)) return rc;          // the walk, timed from ev0
@@ -258,12 +297,18 @@ extern "C" int bsgs_kangaroo_run_dptable(bsgs_dev *d, uint32_t steps, bsgs_kanga
     return BSGS_OK;
 }
 
-extern "C" int bsgs_kangaroo_dptable_insert(bsgs_dev *d, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs,
-                                            uint32_t *nrecs, uint64_t *n_entries, uint64_t *dropped)
+extern "C" int bsgs_kangaroo_run_dptable(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen,
+                                         uint64_t *n_entries, uint64_t *dropped, float *kernel_ms)
+{
+    return bsgs_kang_dpt_run(d, false, steps, recs, max_recs, nrecs, n_seen, n_entries, dropped, kernel_ms);
+}
+
+int bsgs_kang_dpt_insert(bsgs_dev *d, bool keyed, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs, uint32_t *nrecs,
+                         uint64_t *n_entries, uint64_t *dropped)
 {
     if (!d || !nrecs || (n && !recs_in)) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, true)) return rc;
+    if (int rc = dpt_herd(d, &k, true, keyed ? DPT_KEYED : DPT_UNKEYED)) return rc;
     const uint64_t count = n;
     if (int rc = bsgs_kang_table_stage(d, k, k->dpt_out, recs_in, &count)) return rc;
     if (int rc = dpt_insert(d, k)) return rc;
@@ -280,12 +325,18 @@ extern "C" int bsgs_kangaroo_dptable_insert(bsgs_dev *d, const bsgs_kangaroo_rec
     return bsgs_kang_table_entries(d, &k->dpt, n_entries);
 }
 
+extern "C" int bsgs_kangaroo_dptable_insert(bsgs_dev *d, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs,
+                                            uint32_t *nrecs, uint64_t *n_entries, uint64_t *dropped)
+{
+    return bsgs_kang_dpt_insert(d, false, recs_in, n, recs_out, max_recs, nrecs, n_entries, dropped);
+}
+
 extern "C" int bsgs_kangaroo_dptable_load(bsgs_dev *d, const bsgs_kangaroo_dp_entry *entries, uint64_t n, uint64_t *n_stored, uint64_t *n_duplicate, uint64_t *n_zero,
                                           uint64_t *n_full, uint64_t *n_entries)
 {
     if (!d || (n && !entries)) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, true)) return rc;
+    if (int rc = dpt_herd(d, &k, true, DPT_EITHER)) return rc;
     if (n > KT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "%llu entries to load: at most 2^31", (unsigned long long)n);
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipMemsetAsync(k->dpt.ctr + CTR_STORED, 0, 32, d->stream));
@@ -321,7 +372,7 @@ extern "C" int bsgs_kangaroo_dptable_read(bsgs_dev *d, bsgs_kangaroo_dp_entry *e
 {
     if (!d || !n) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, true)) return rc;
+    if (int rc = dpt_herd(d, &k, true, DPT_EITHER)) return rc;
     HIPCHK(hipSetDevice(d->id));
     uint64_t held = 0;
     if (int rc = bsgs_kang_table_entries(d, &k->dpt, &held)) return rc;

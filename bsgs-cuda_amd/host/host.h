@@ -233,6 +233,9 @@ int kangaroo_selftest(const std::vector<std::string> &args);
 int kangaroo_work_selftest(const std::vector<std::string> &args);
 int kangaroo_roundtrip_selftest(const std::vector<std::string> &args);
 int kangaroo_dpdev_selftest(const std::vector<std::string> &args);               // -selftest kangaroo-dpdev [sym]: the hand-back rule of -kdpdev on scripted records and pairs
+int kangaroo_dpkeys_selftest(const std::vector<std::string> &args);              // -selftest kangaroo-dpkeys [sym]: the hand-back rule of -kdpkeys on scripted records and pairs
+int kangaroo_dpkeys_sym_selftest(const std::vector<std::string> &args);          // ... its part for the symmetric walk's table (host_kangaroo_symlist.cpp)
+int kangaroo_dpkeys_plan_selftest(const std::vector<std::string> &args);         // -selftest kangaroo-dpkeys-plan: the plan of -kdpkeys (dp, herd, launch, record buffer, capacity)
 int kangaroo_dpdev_plan_selftest(const std::vector<std::string> &args);          // -selftest kangaroo-dpdev-plan: the plan of -kdpdev (dp, herd, launch, record buffer, capacity)
 int kangaroo_sym_selftest(const std::vector<std::string> &args);                 // -selftest kangaroo-sym: the symmetric walk's table
 int kangaroo_sym_roundtrip_selftest(const std::vector<std::string> &args);       // -selftest kangaroo-sym-roundtrip: through a version-2 work file

@@ -342,6 +342,7 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-ksteps") { c.ksteps = strtoull(next().c_str(), nullptr, 10); if (!c.ksteps) die("-ksteps must be at least 1"); }
         else if (a == "-kcpuseed") c.cpuseed = true;
         else if (a == "-kdpdev") c.kdpdev = true;
+        else if (a == "-kdpkeys") c.kdpkeys = true;
         else if (a == "-kdpn") { c.kdpn = strtoull(next().c_str(), nullptr, 0); if (!c.kdpn || c.kdpn > (1ull << 31)) die("-kdpn must be 1..2^31"); }
         else if (a == "-ksym") ksym = true;
         else if (a == "-kwalk") { const std::string w = next(); if (w != "plain" && w != "sym") die("-kwalk must be plain or sym"); kwalk_sym = w == "sym"; }
@@ -352,9 +353,22 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else die("Unknown parameter with -kangaroo: " + a);
     }
     // -kdpdev: the table of distinguished points of the one-key search, plain and -ksym, in device memory; every refusal before any device is looked for
-    if (c.kdpn && !c.kdpdev) die("-kdpn belongs to -kdpdev (the capacity of the table in GPU memory)");
+    if (c.kdpn && !c.kdpdev && !c.kdpkeys) die("-kdpn belongs to -kdpdev or -kdpkeys (the capacity of the table in GPU memory)");
+    // -kdpkeys: the same for the list of -infile, plain and -kwalk sym, with an owner per entry
+    if (c.kdpkeys) {
+        if (c.kdpdev) die("-kangaroo -kdpkeys cannot be combined with -kdpdev (-kdpdev is the table of one key, -kdpkeys that of a key list)");
+        if (c.pub_given) die("-kangaroo -kdpkeys cannot be combined with -pb (the table in GPU memory of one key is -kdpdev)");
+        if (c.infile.empty()) die("-kangaroo -kdpkeys needs -infile (it keeps the table of a key list in GPU memory)");
+        if (!c.ktames.empty() || !c.ktamesgen.empty() || !c.ktamesmerge.empty() || c.ktamesdev || !c.ktamesfrom.empty() || c.ktnplan || c.ktn)
+            die("-kangaroo -kdpkeys cannot be combined with -ktames, -ktamessym, -ktamesgen or their flags (a tame table is matched or grown by calls of its own)");
+        if (c.devices.find(',') != std::string::npos) die("-kangaroo -kdpkeys takes one -d entry (several engines would need one table for all of them)");
+        if (c.devices.empty()) {
+            c.devices = "0";
+            printf("Kangaroo -kdpkeys: no -d given, one engine on GPU #0\n");
+        }
+    }
     if (c.kdpdev) {
-        if (!c.infile.empty()) die("-kangaroo -kdpdev cannot be combined with -infile (the table in GPU memory pairs the records of one key)");
+        if (!c.infile.empty()) die("-kangaroo -kdpdev cannot be combined with -infile (the table in GPU memory pairs the records of one key; -kdpkeys keeps the table of a key list there)");
         if (!c.ktames.empty() || !c.ktamesgen.empty() || !c.ktamesmerge.empty())
             die("-kangaroo -kdpdev cannot be combined with -ktames, -ktamessym, -ktamesgen or -ktamesmerge (a tame table is matched or grown by calls of its own)");
         if (c.devices.find(',') != std::string::npos) die("-kangaroo -kdpdev takes one -d entry (several engines would need one table for all of them)");

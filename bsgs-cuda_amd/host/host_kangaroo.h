@@ -81,7 +81,8 @@ struct KangConfig {
     uint64_t ktnplan = 0;                          // -ktnplan N with -ktamesgen: the walk is planned for a table of N entries (0: for -ktn)
     bool range_given = false;                      // -pk or -pke stood on the command line
     bool kdpdev = false;                           // -kdpdev with -pb, plain and -ksym: the table of distinguished points lives in device memory (bsgs_kangaroo_run_dptable)
-    uint64_t kdpn = 0;                             // -kdpn N with -kdpdev: the capacity of that table (default: dpdev_capacity)
+    uint64_t kdpn = 0;                             // -kdpn N with -kdpdev or -kdpkeys: the capacity of that table (default: dpdev_capacity)
+    bool kdpkeys = false;                          // -kdpkeys with -infile, plain and -kwalk sym: the list search's table lives in device memory (bsgs_kangaroo_run_dptable_keys)
 };
 KangConfig parse_kangaroo_args(int argc, char **argv);
 

@@ -17,6 +17,7 @@ template <class Table> struct ListSearch : Mode {
     ListSearch(const KangConfig &c, const std::vector<Affine> &P) : c(c), P(P), L((uint32_t)P.size())
     {
         if (c.cpuseed) herd_label = "herds (host), engine ";
+        if (c.kdpkeys) { counts_records = false; bound_launch = true; dp_free = c.dp < 0; }      // -kdpkeys: the launch counts, and is kept within the record buffer
     }
     // ---- what a walk supplies
     virtual void own_settings(Prologue &) {}                                       // its header fields, and its part of "made with other settings"
@@ -28,6 +29,8 @@ template <class Table> struct ListSearch : Mode {
     virtual void put_key(bsgs_kangaroo_state &s, uint32_t key) const = 0;          // the host's comb: the key into a state whose flags are the type
     virtual void print_expectation(const Prologue &p) const = 0;
     virtual void add_record(const bsgs_kangaroo_record &r, uint32_t kid, std::vector<Event> &ev) = 0;
+    // -kdpkeys: a record (as the walk wrote it) that the device table handed back as a duplicate, against the stored entry it came with
+    virtual void add_pair_record(const bsgs_kangaroo_record &stored, const bsgs_kangaroo_record &r, uint32_t kid, std::vector<Event> &ev) = 0;
     virtual void save_own(WorkHeader &) const {}
     virtual void closing() const {}                                                // its line between the job's figures and the engines'
 
@@ -63,6 +66,21 @@ template <class Table> struct ListSearch : Mode {
             if (Q[k].inf) { presolved[k] = true; table->presolve(k, base); if (p.resume) found_n++; else report(k); Q[k] = hs::G; }
             hs::affine_to_le(Q[k], &qxy[64 * (size_t)k], &qxy[64 * (size_t)k + 32]);
         }
+        const uint64_t file_entries = p.resume ? p.wf.h.table : 0;
+        if (c.kdpkeys && p.resume) {                                               // the file's entries go to the device once they are verified (resumed()); tag 0 stays here
+            std::vector<uint8_t> own;
+            for (uint64_t i = 0; i < p.wf.h.table; i++) {
+                const uint8_t *en = &p.wf.table[32 * i];
+                uint64_t k64; uint32_t owner;
+                memcpy(&k64, en, 8); memcpy(&owner, en + 28, 4);
+                if (!table->owner_fits(owner)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
+                std::vector<uint8_t> &to = k64 ? pending : own;
+                to.insert(to.end(), en, en + 32);
+            }
+            p.wf.table.swap(own);
+            p.wf.h.table = p.wf.table.size() / 32;
+            dev_entries = pending.size() / 32;
+        }
         if (p.resume) {                                                            // the file's solved keys are in win.txt already: counted, not written again
             const uint32_t before = table->solved();
             if (!restore_table(p)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
@@ -71,6 +89,12 @@ template <class Table> struct ListSearch : Mode {
         }
         open0 = L - table->solved();
         if (!open0) printf("Found %d of %u\n", found_n, L);
+        if (c.kdpkeys && open0) {                                                  // the table in device memory: -kdpdev's rule with sqrt(L_open W) in the place of sqrt(W)
+            const double sq = std::sqrt((double)open0 * (double)p.W);
+            capacity = dpdev_capacity(sq, c.kdpn);
+            while (p.resume && capacity < 2 * file_entries && capacity < (1ull << 31)) capacity *= 2;      // (a file that holds more than this run would plan for)
+            dp_fixed = c.dp >= 0 ? c.dp : (int)dpdev_dp(sq, capacity);
+        }
         return open0 != 0;
     }
     // after the prologue: the expectation, the assignment of wild kangaroos to keys (-wl: as the saved states name it), the offsets of the initial herds in
@@ -94,7 +118,7 @@ template <class Table> struct ListSearch : Mode {
                 keys[(uint64_t)e * (kn - half) + (i - half)] = k;
             }
             asg->restore(keys, *table);
-            printf("Resumed: %llu steps, %zu DPs, %u of %u keys solved\n", (unsigned long long)p.wf.h.steps, table->size(), table->solved(), L);
+            printf("Resumed: %llu steps, %zu DPs, %u of %u keys solved\n", (unsigned long long)p.wf.h.steps, table_size(), table->solved(), L);
         }
         if (c.cpuseed) comb.reset(new Comb());
         steps_mark = s.steps.load();
@@ -165,10 +189,74 @@ template <class Table> struct ListSearch : Mode {
         }
         return nullptr;
     }
+    // -kdpkeys: the keyed table after the key list (a walk's setup() ends with it)
+    const char *begin_table(bsgs_dev *dev) const
+    {
+        return !c.kdpkeys || bsgs_kangaroo_dptable_begin_keys(dev, capacity) == BSGS_OK ? nullptr : "bsgs_kangaroo_dptable_begin_keys";
+    }
+    // -kdpkeys: the walk, the insert and the pairing in device memory; only the hand-backs reach the collector, and the DP count is the walk's
+    int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &s) override
+    {
+        if (!c.kdpkeys) return Mode::launch(dev, e, steps, recs, cap, n, dropped, s);
+        uint64_t seen = 0, entries = 0;
+        const int rc = bsgs_kangaroo_run_dptable_keys(dev, steps, recs, cap, n, &seen, &entries, dropped, nullptr);
+        if (rc != BSGS_OK) return rc;
+        uint64_t dead = 0;
+        for (uint32_t i = 0; i < *n; i++) dead += recs[i].reserved != BSGS_KANGAROO_DPT_STORED && (recs[i].flags & BSGS_KANGAROO_DEAD);
+        s.dps += seen - std::min(seen, dead);
+        dev_entries = entries;
+        return rc;
+    }
+    // -kdpkeys -wl: the file's entries, verified, into the device table; a tag that occurs twice, is 0 or finds no slot: the section does not load
+    std::string resumed(bsgs_dev *dev, uint32_t e, Shared &s) override
+    {
+        (void)e; (void)s;
+        if (!c.kdpkeys || pending.empty()) return "";
+        uint64_t stored_n = 0, dup = 0, zero = 0, full = 0, entries = 0;
+        const auto ts = Clock::now();
+        if (bsgs_kangaroo_dptable_load(dev, (const bsgs_kangaroo_dp_entry *)pending.data(), pending.size() / 32, &stored_n, &dup, &zero, &full, &entries) != BSGS_OK)
+            return std::string("bsgs_kangaroo_dptable_load: ") + bsgs_last_error();
+        if (dup || full || zero) return "-kangaroo -wl: the table section of " + pro->wl_path + " does not load";
+        printf("[startup] %-44s %.3fs\n", ("table (GPU memory), " + std::to_string(entries) + " entries").c_str(), since(ts));
+        dev_entries = entries;
+        std::vector<uint8_t>().swap(pending);
+        return "";
+    }
+    // -kdpkeys: the device table as it stands, for save()
+    std::string fetch(bsgs_dev *dev, uint32_t e, Shared &s) override
+    {
+        (void)e; (void)s;
+        if (!c.kdpkeys) return "";
+        uint64_t n = 0;
+        if (bsgs_kangaroo_dptable_read(dev, nullptr, 0, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();      // the count alone
+        std::vector<uint8_t> got(32 * n);
+        if (n && bsgs_kangaroo_dptable_read(dev, (bsgs_kangaroo_dp_entry *)got.data(), n, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();
+        if (32 * n != got.size()) return "bsgs_kangaroo_dptable_read: the table changed between the count and the read";
+        std::lock_guard<std::mutex> lk(dev_m);
+        dev_table.swap(got);
+        return "";
+    }
+    size_t table_size() const { return table->size() + (size_t)dev_entries.load(); }      // "in the table": the host's entries and the device's
     bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &s) override
     {
         std::vector<Event> ev;
-        add_record(r, (uint32_t)(e * pro->pl.kn + r.kangaroo), ev);
+        const uint32_t kid = (uint32_t)(e * pro->pl.kn + r.kangaroo);
+        if (c.kdpkeys) {                                                           // a hand-back: `reserved` = reason | key << 8, or the stored half of a pair
+            if (r.reserved == BSGS_KANGAROO_DPT_STORED) { stored = r; have_stored = true; return true; }      // the entry the next record met
+            bsgs_kangaroo_record w = r;                                            // the record as the walk wrote it
+            w.reserved = r.reserved >> BSGS_KANGAROO_DPT_KEY_SHIFT;
+            if ((r.reserved & ((1u << BSGS_KANGAROO_DPT_KEY_SHIFT) - 1u)) == BSGS_KANGAROO_DPT_DUPLICATE) {
+                if (!have_stored) return true;                                     // (never: the device does not split a pair)
+                have_stored = false;
+                if (!table->owner_fits(stored.flags)) {                            // the table names a key the list does not have
+                    std::lock_guard<std::mutex> lk(s.err_m);
+                    if (s.err.empty()) s.err = "-kangaroo -kdpkeys: the table in GPU memory is damaged: an entry names owner " + std::to_string(stored.flags) + ", the list has " + std::to_string(L) + " keys";
+                    s.failed = true; s.stop = true;
+                    return false;
+                }
+                add_pair_record(stored, w, kid, ev);
+            } else add_record(w, kid, ev);                                         // DEAD, tag 0, a full device table -- the host's own map, as without the flag
+        } else add_record(r, kid, ev);
         for (const Event &x : ev) if (x.what == Table::RESEED) s.push_reseed(e, r.kangaroo);
         on_events(ev);
         return true;
@@ -188,9 +276,12 @@ template <class Table> struct ListSearch : Mode {
     }
     const WorkKeys *save(WorkHeader &h, std::vector<uint8_t> &entries) override
     {
-        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.table = table->size();
+        std::lock_guard<std::mutex> lk(dev_m);
+        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.table = table->size() + dev_table.size() / 32;
         save_own(h);
-        entries.reserve(32 * table->size());
+        entries.swap(dev_table);                                                   // -kdpkeys: what fetch() read when the herds were downloaded -- moved, not copied: every
+        std::vector<uint8_t>().swap(dev_table);                                    // save follows a fetch() of its own
+        entries.reserve(entries.size() + 32 * table->size());
         table->write_entries(entries);
         table->write_keys(wk);
         return &wk;
@@ -215,6 +306,13 @@ template <class Table> struct ListSearch : Mode {
     uint32_t open0 = 0, last_solved = 0;
     uint64_t half = 0, steps_mark = 0;
     double overhead = 0.0, exp_lo = 0.0, exp_hi = 0.0;
+    // -kdpkeys
+    uint64_t capacity = 0;                         // of the device table
+    std::atomic<uint64_t> dev_entries{0};          // entries in it after the last launch
+    std::vector<uint8_t> pending, dev_table;       // -wl: the file's entries on their way to the device; the device table as fetch() read it
+    std::mutex dev_m;
+    bsgs_kangaroo_record stored;                   // the first record of a handed-back pair, until its record comes
+    bool have_stored = false;
 };
 
 // bsgs_mi355x -kangaroo -infile FILE with the walk of ModeT: every key of the list in [pk, pke] with ONE herd per engine
@@ -232,6 +330,12 @@ template <class ModeT> int list_main(const KangConfig &c)
     ModeT mode(c, P);
     p.complete(c, mode);                                                           // dp, kn, the jump mean and the launch length from W, as for one key
     if (!p.go) return 0;
+    if (c.kdpkeys) {
+        uint64_t slots = 128;
+        while (slots < 2 * (mode.capacity + p.pl.cap)) slots *= 2;
+        printf("Kangaroo: distinguished points stay in GPU memory (-kdpkeys): table of %llu entries, %llu slots, %.2f GiB; hand-backs only cross the bus\n",
+               (unsigned long long)mode.capacity, (unsigned long long)slots, (double)slots * 32.0 / 1073741824.0);
+    }
     Shared sh(p);
     mode.prepare(p, sh);
     const Outcome o = run(c, p, sh, mode);
@@ -241,7 +345,7 @@ template <class ModeT> int list_main(const KangConfig &c)
     else if (o != DONE) printf("\nKangaroo: stopped after %llu steps (%s), %u of %u keys open\n", (unsigned long long)sh.steps.load(), o == BUDGET ? "-ksteps" : "signal",
                                L - table.solved(), L);
     printf("Job time %.2fs, %.3e kangaroo steps, %llu DPs (%zu in the table, %llu dropped), %llu false matches, %llu re-seeds, %llu links kept, %llu links resolved\n", p.elapsed_before + since(p.t0),
-           (double)sh.steps.load(), (unsigned long long)sh.dps.load(), table.size(), (unsigned long long)sh.dropped.load(), (unsigned long long)table.false_matches(),
+           (double)sh.steps.load(), (unsigned long long)sh.dps.load(), mode.table_size(), (unsigned long long)sh.dropped.load(), (unsigned long long)table.false_matches(),
            (unsigned long long)table.reseeds(), (unsigned long long)table.links_kept(), (unsigned long long)table.links_resolved());
     mode.closing();
     for (uint32_t e = 0; e < p.pl.engines; e++) printf("Engine %u (GPU #%d): %llu records\n", e, p.gpus[e], (unsigned long long)sh.engine_records[e]);

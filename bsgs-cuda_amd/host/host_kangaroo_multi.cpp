@@ -67,13 +67,24 @@ void MultiKeyTable::add(const uint8_t x[32], u128 d, uint32_t kid, uint32_t flag
     if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; ev.push_back(Event{RESEED, kid, 0, Scalar()}); return; }
     uint64_t k64;
     memcpy(&k64, x, 8);
-    const uint32_t owner = flags & BSGS_KANGAROO_WILD ? 1u + ((flags >> BSGS_KANGAROO_KEY_SHIFT) & 0xFFFFu) : 0u;
-    auto it = map_.find(k64);
+    const uint32_t owner = record_owner(flags);
+    auto it = map_.find(k64);                                         // look the tag up ...
     if (it == map_.end()) { map_.emplace(k64, Entry{(i128)d, kid, owner}); ev.push_back(Event{NEW, 0, 0, Scalar()}); return; }
-    const Entry &e = it->second;
+    judge(it->second, (i128)d, kid, owner, ev);                       // ... and judge this record against that entry
+}
+
+void MultiKeyTable::add_pair(i128 entry_d, uint32_t entry_kid, uint32_t entry_owner, u128 d, uint32_t kid, uint32_t flags, std::vector<Event> &ev)
+{
+    if (flags & BSGS_KANGAROO_DEAD) { reseeds_++; ev.push_back(Event{RESEED, kid, 0, Scalar()}); return; }      // (never: the device hands a DEAD record back alone)
+    judge(Entry{entry_d, entry_kid, entry_owner}, (i128)d, kid, record_owner(flags), ev);
+}
+
+// a record (d, kid, owner), not DEAD, against the stored entry of its x
+void MultiKeyTable::judge(const Entry &e, i128 d, uint32_t kid, uint32_t owner, std::vector<Event> &ev)
+{
     if (e.kid == kid) { ev.push_back(Event{REPEAT, 0, 0, Scalar()}); return; }
     // an owner whose key is solved counts as tame: d' = d + (k_k - a)
-    i128 d1 = e.d, d2 = (i128)d;
+    i128 d1 = e.d, d2 = d;
     uint32_t o1 = e.owner, o2 = owner;
     if (o1 && known_[o1 - 1]) { d1 += off_[o1 - 1]; o1 = 0; }
     if (o2 && known_[o2 - 1]) { d2 += off_[o2 - 1]; o2 = 0; }
@@ -139,8 +150,9 @@ bool MultiKeyTable::restore(const uint8_t *entries, uint64_t n, uint64_t false_m
     return true;
 }
 
-// one scripted record into the table, its event lines printed; false: the record does not parse
-static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::string &rec)
+// one scripted record into the table, its event lines printed; false: the record does not parse.  stored (-selftest kangaroo-dpkeys): the fields of the
+// S, item in front of the record -- tag, d, kangaroo, owner -- and the record is judged against that entry as a pair
+static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::string &rec, const std::vector<std::string> *stored = nullptr)
 {
     const std::vector<std::string> f = kang::split_commas(rec);
     if (f.size() != 4 || f[0].empty() || !strchr("TWD", f[0][0]) || (f[0][0] != 'W' && f[0].size() != 1)) return false;
@@ -156,7 +168,15 @@ static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::
     uint8_t xb[32];
     hs::fe_to_le(x, xb);
     std::vector<MultiKeyTable::Event> ev;
-    tab.add(xb, ((u128)dd.l[1] << 64) | dd.l[0], (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, ev);
+    if (stored) {
+        Scalar tag, ed;
+        if (stored->size() != 5 || f[0][0] == 'D' || !hs::fe_from_hex(tag, (*stored)[1]) || tag.l[1] || tag.l[2] || tag.l[3] || !hs::fe_from_hex(ed, (*stored)[2]) || ed.l[2] || ed.l[3]) return false;
+        if (x.l[0] != tag.l[0]) { fprintf(stderr, "the record does not share the tag of the stored entry it is paired with\n"); return false; }
+        const uint32_t owner = (uint32_t)strtoul((*stored)[4].c_str(), nullptr, 10);
+        if (!tab.owner_fits(owner)) { fprintf(stderr, "the table is damaged: an entry names owner %u, the list has %zu keys\n", owner, n_keys); return false; }
+        tab.add_pair((i128)(((u128)ed.l[1] << 64) | ed.l[0]), (uint32_t)strtoul((*stored)[3].c_str(), nullptr, 10), owner, ((u128)dd.l[1] << 64) | dd.l[0],
+                     (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, ev);
+    } else tab.add(xb, ((u128)dd.l[1] << 64) | dd.l[0], (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, ev);
     for (const MultiKeyTable::Event &e : ev) switch (e.what) {
         case MultiKeyTable::NEW: printf("new\n"); break;
         case MultiKeyTable::REPEAT: printf("repeat\n"); break;
@@ -194,6 +214,49 @@ int kangaroo_multi_selftest(const std::vector<std::string> &a)
     presolve_scripted(tab, pubs, lo);
     for (size_t i = 3; i < a.size(); i++) if (!multi_scripted_record(tab, pubs.size(), a[i])) return 2;
     print_summary(tab);
+    return 0;
+}
+
+// -selftest kangaroo-dpkeys [sym] <pk hex> <pke hex> <pubkey>[,<pubkey>...] <item>...: the hand-back rule of -kdpkeys without a GPU.  An item is a scripted
+// record as -selftest kangaroo-multi (sym: kangaroo-symlist) takes it -- what the device hands back alone: DEAD, tag 0, a full table -- and goes through the
+// host's own map; or S,<tag hex>,<d hex>,<kangaroo>,<owner> followed by its record: a duplicate, judged against the stored entry it came with.  The same event
+// and summary lines.
+int kangaroo_dpkeys_selftest(const std::vector<std::string> &args)
+{
+    if (!args.empty() && args[0] == "sym") return kangaroo_dpkeys_sym_selftest(std::vector<std::string>(args.begin() + 1, args.end()));
+    const std::vector<std::string> &a = args;
+    if (a.size() < 3) return 2;
+    Scalar lo, hi; u128 W;
+    std::vector<Affine> pubs;
+    if (!kang::parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
+    MultiKeyTable tab(lo, W, pubs);
+    presolve_scripted(tab, pubs, lo);
+    for (size_t i = 3; i < a.size(); i++) {
+        if (a[i].compare(0, 2, "S,") != 0) { if (!multi_scripted_record(tab, pubs.size(), a[i])) return 2; continue; }
+        if (i + 1 >= a.size()) return 2;                              // a stored entry without its record
+        const std::vector<std::string> s = kang::split_commas(a[i]);
+        if (!multi_scripted_record(tab, pubs.size(), a[++i], &s)) return 2;
+    }
+    print_summary(tab);
+    return 0;
+}
+
+// -selftest kangaroo-dpkeys-plan <pk hex> <pke hex> <CUs> <min launch> <dp or -1> <kn or 0> <kdpn or 0> <L>: the plan of -kdpkeys for one engine and L open
+// keys without a GPU -- -kdpdev's with sqrt(L W) in the place of sqrt(W) for the capacity and dp -- as -selftest kangaroo-dpdev-plan prints it
+int kangaroo_dpkeys_plan_selftest(const std::vector<std::string> &a)
+{
+    if (a.size() != 8) return 2;
+    kang::KangConfig c;
+    c.pk = a[0]; c.pke = a[1];
+    kang::Prologue p(c);
+    const int cus = atoi(a[2].c_str()), dp_arg = atoi(a[4].c_str());
+    const uint64_t L = strtoull(a[7].c_str(), nullptr, 0);
+    if (!L || L > BSGS_KANGAROO_MAX_KEYS) return 2;
+    const double sq = std::sqrt((double)L * (double)p.W);
+    const uint64_t capacity = kang::dpdev_capacity(sq, strtoull(a[6].c_str(), nullptr, 0));
+    kang::Plan pl = kang::plan_herd(p.sqrtW, 1, cus, dp_arg >= 0 ? dp_arg : (int)kang::dpdev_dp(sq, capacity), strtoull(a[5].c_str(), nullptr, 0));
+    kang::plan_launch(pl, p.sqrtW, 0.0, atof(a[3].c_str()), true, dp_arg < 0);
+    printf("plan %u %llu %u %u %u %llu\n", pl.dp, (unsigned long long)pl.kn, pl.G, pl.S, pl.cap, (unsigned long long)capacity);
     return 0;
 }
 
@@ -263,13 +326,20 @@ struct ListMode : ListSearch<MultiKeyTable> {
     {
         const Plan &pl = pro->pl;
         if (bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup";
-        return bsgs_kangaroo_set_keys(dev, qxy.data(), L) == BSGS_OK ? nullptr : "bsgs_kangaroo_set_keys";
+        if (bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) return "bsgs_kangaroo_set_keys";
+        return begin_table(dev);
     }
     void add_record(const bsgs_kangaroo_record &r, uint32_t kid, std::vector<MultiKeyTable::Event> &ev) override
     {
         u128 d;
         memcpy(&d, r.d, 16);
         table->add(r.x, d, kid, r.flags, ev);
+    }
+    void add_pair_record(const bsgs_kangaroo_record &st, const bsgs_kangaroo_record &r, uint32_t kid, std::vector<MultiKeyTable::Event> &ev) override
+    {
+        u128 d; i128 ed;
+        memcpy(&d, r.d, 16); memcpy(&ed, st.d, 16);
+        table->add_pair(ed, st.kangaroo, st.flags, d, kid, r.flags, ev);
     }
     // (verify_q stays null: the engines hold the key list)  owner 0 tame, 1 + k a wild kangaroo of key k
     uint32_t entry_flags(uint32_t owner) const override { return owner ? BSGS_KANGAROO_WILD | (owner - 1u) << BSGS_KANGAROO_KEY_SHIFT : 0u; }

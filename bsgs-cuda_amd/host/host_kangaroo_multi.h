@@ -17,6 +17,10 @@ public:
     void presolve(uint32_t k, const Scalar &key);
     // one record into the table; its events are appended to ev (one record can solve several keys through links)
     void add(const uint8_t x[32], unsigned __int128 d, uint32_t kid, uint32_t flags, std::vector<Event> &ev);
+    // -kdpkeys: a record the device table handed back as a duplicate, against the stored entry it came with (d, kangaroo, owner word): exactly the events
+    // add() gives for a record that meets that entry in the map; never NEW, and the map is not touched
+    void add_pair(__int128 entry_d, uint32_t entry_kid, uint32_t entry_owner, unsigned __int128 d, uint32_t kid, uint32_t flags, std::vector<Event> &ev);
+    bool owner_fits(uint32_t owner) const { return owner <= pubs_.size(); }         // an owner word of this list: 0, or 1 + a list position
     // key k learnt outside the table (a wild start at infinity): the same consequences as a collision that solves it
     void found(uint32_t k, const Scalar &key, std::vector<Event> &ev);
     bool known(uint32_t k) const { return known_[k]; }
@@ -37,6 +41,8 @@ private:
     struct Entry { __int128 d; uint32_t kid, owner; };           // owner: 0 tame, 1 + list position for a wild kangaroo of that key
     struct Link { uint32_t j, k; __int128 delta; bool alive; };  // k_j = k_k + delta
     bool verify(uint32_t k, __int128 off, Scalar *key) const;
+    static uint32_t record_owner(uint32_t flags) { return flags & BSGS_KANGAROO_WILD ? 1u + ((flags >> BSGS_KANGAROO_KEY_SHIFT) & 0xFFFFu) : 0u; }
+    void judge(const Entry &e, __int128 d, uint32_t kid, uint32_t owner, std::vector<Event> &ev);
     const Scalar a_;
     const unsigned __int128 W_;
     const std::vector<Affine> pubs_;

@@ -66,67 +66,22 @@ public:
     // one record into the table; key: the record's fourth word, the key of its kangaroo (below the list's length for a wild record)
     void add(const uint8_t x[32], u128 d, uint32_t kid, uint32_t flags, uint32_t key, std::vector<Event> &ev)
     {
-        if (flags & BSGS_KANGAROO_DEAD) {
-            reseeds_++;
-            if (flags & BSGS_KANGAROO_CYCLE) cycles_++;
-            ev.push_back(Event{RESEED, kid, 0, Scalar()});
-            return;
-        }
+        if (dead(kid, flags, ev)) return;
         uint64_t k64;
         memcpy(&k64, x, 8);
-        const bool wild = flags & BSGS_KANGAROO_WILD;
-        const uint32_t owner = wild ? (1u + key) | (flags & BSGS_KANGAROO_NEG ? OWNER_NEG : 0u) : 0u;
-        auto it = map_.find(k64);
+        const uint32_t owner = record_owner(flags, key);
+        auto it = map_.find(k64);                                     // look the tag up ...
         if (it == map_.end()) { map_.emplace(k64, Entry{(i128)d, kid, owner}); ev.push_back(Event{NEW, 0, 0, Scalar()}); return; }
-        const Entry &e = it->second;
-        // its own point again with the offset and the owner it had: the walk is a function of x, so it runs a cycle longer than the window.  (A kangaroo's
-        // number outlives a re-seed: on a point of its earlier life, with another offset, key or sign, it is taken as any other kangaroo below.)
-        if (e.kid == kid && e.owner == owner && e.d == (i128)d) {
-            reseeds_++; cycles_++;
-            ev.push_back(Event{REPEAT, 0, 0, Scalar()});
-            ev.push_back(Event{RESEED, kid, 0, Scalar()});
-            return;
-        }
-        // sigma and key of both; an owner whose key is solved counts as tame: d' = d + sigma k''
-        i128 d1 = e.d, d2 = (i128)d;
-        int s1 = sigma(e.owner), s2 = sigma(owner);
-        const uint32_t k1 = (e.owner & ~OWNER_NEG) - 1u, k2 = (owner & ~OWNER_NEG) - 1u;      // (meaningless for sigma 0)
-        if (s1 && known_[k1]) { d1 += s1 * kpp_[k1]; s1 = 0; }
-        if (s2 && known_[k2]) { d2 += s2 * kpp_[k2]; s2 = 0; }
-        auto reseed = [&]() { reseeds_++; ev.push_back(Event{RESEED, kid, 0, Scalar()}); };
-        if (!s1 && !s2) { reseed(); return; }
-        Scalar kv;
-        if (!s1 || !s2) {                                             // tame d_T, wild (sigma, d_W) of key k: k'' = sigma (eps d_T - d_W)
-            const i128 dt = s1 ? d2 : d1, dw = s1 ? d1 : d2;
-            const int sw = s1 ? s1 : s2;
-            const uint32_t k = s1 ? k1 : k2;
-            if (verify(k, sw * (dt - dw), &kv) || verify(k, sw * (-dt - dw), &kv)) { found(k, kv, ev); return; }
-            false_++;
-            ev.push_back(Event{FALSE_MATCH, 0, 0, Scalar()});
-            reseed();
-            return;
-        }
-        if (k1 == k2) {                                               // the rule of one key: (sigma1 - eps sigma2) k'' = eps d2 - d1, the divisor +-2 or 0
-            bool tried = false;
-            for (int eps = 1; eps >= -1; eps -= 2) {
-                const int den = s1 - eps * s2;
-                if (!den) continue;
-                tried = true;
-                const i128 num = eps * d2 - d1;
-                if (num & 1) continue;                                // (no integer solves it: mod n it lies far outside the interval)
-                if (verify(k1, num / den, &kv)) { found(k1, kv, ev); return; }
-            }
-            if (tried) { false_++; ev.push_back(Event{FALSE_MATCH, 0, 0, Scalar()}); }
-            reseed();
-            return;
-        }
-        adj_[k1].push_back((uint32_t)links_.size());
-        adj_[k2].push_back((uint32_t)links_.size());
-        links_.push_back(Link{k1, k2, s1, s2, d1, d2, true});
-        kept_++; live_links_++;
-        ev.push_back(Event{LINK, k1, k2, Scalar()});
-        reseed();
+        judge(it->second, (i128)d, kid, owner, ev);                   // ... and judge this record against that entry
     }
+    // -kdpkeys: a record the device table handed back as a duplicate, against the stored entry it came with (d, kangaroo, owner word): exactly the events
+    // add() gives for a record that meets that entry in the map; never NEW, and the map is not touched
+    void add_pair(i128 entry_d, uint32_t entry_kid, uint32_t entry_owner, u128 d, uint32_t kid, uint32_t flags, uint32_t key, std::vector<Event> &ev)
+    {
+        if (dead(kid, flags, ev)) return;                             // (never: the device hands a DEAD record back alone)
+        judge(Entry{entry_d, entry_kid, entry_owner}, (i128)d, kid, record_owner(flags, key), ev);
+    }
+    bool owner_fits(uint32_t owner) const { return (owner & ~OWNER_NEG) <= pubs_.size() && owner != OWNER_NEG; }      // an owner word of this list
     bool known(uint32_t k) const { return known_[k]; }
     const Scalar &key(uint32_t k) const { return key_[k]; }
     uint32_t solved() const { return solved_; }
@@ -182,6 +137,66 @@ public:
     }
 private:
     struct Entry { i128 d; uint32_t kid, owner; };
+    static uint32_t record_owner(uint32_t flags, uint32_t key) { return flags & BSGS_KANGAROO_WILD ? (1u + key) | (flags & BSGS_KANGAROO_NEG ? OWNER_NEG : 0u) : 0u; }
+    bool dead(uint32_t kid, uint32_t flags, std::vector<Event> &ev)
+    {
+        if (!(flags & BSGS_KANGAROO_DEAD)) return false;
+        reseeds_++;
+        if (flags & BSGS_KANGAROO_CYCLE) cycles_++;
+        ev.push_back(Event{RESEED, kid, 0, Scalar()});
+        return true;
+    }
+    // a record (d, kid, owner), not DEAD, against the stored entry of its x
+    void judge(const Entry &e, i128 d, uint32_t kid, uint32_t owner, std::vector<Event> &ev)
+    {
+        // its own point again with the offset and the owner it had: the walk is a function of x, so it runs a cycle longer than the window.  (A kangaroo's
+        // number outlives a re-seed: on a point of its earlier life, with another offset, key or sign, it is taken as any other kangaroo below.)
+        if (e.kid == kid && e.owner == owner && e.d == d) {
+            reseeds_++; cycles_++;
+            ev.push_back(Event{REPEAT, 0, 0, Scalar()});
+            ev.push_back(Event{RESEED, kid, 0, Scalar()});
+            return;
+        }
+        // sigma and key of both; an owner whose key is solved counts as tame: d' = d + sigma k''
+        i128 d1 = e.d, d2 = d;
+        int s1 = sigma(e.owner), s2 = sigma(owner);
+        const uint32_t k1 = (e.owner & ~OWNER_NEG) - 1u, k2 = (owner & ~OWNER_NEG) - 1u;      // (meaningless for sigma 0)
+        if (s1 && known_[k1]) { d1 += s1 * kpp_[k1]; s1 = 0; }
+        if (s2 && known_[k2]) { d2 += s2 * kpp_[k2]; s2 = 0; }
+        auto reseed = [&]() { reseeds_++; ev.push_back(Event{RESEED, kid, 0, Scalar()}); };
+        if (!s1 && !s2) { reseed(); return; }
+        Scalar kv;
+        if (!s1 || !s2) {                                             // tame d_T, wild (sigma, d_W) of key k: k'' = sigma (eps d_T - d_W)
+            const i128 dt = s1 ? d2 : d1, dw = s1 ? d1 : d2;
+            const int sw = s1 ? s1 : s2;
+            const uint32_t k = s1 ? k1 : k2;
+            if (verify(k, sw * (dt - dw), &kv) || verify(k, sw * (-dt - dw), &kv)) { found(k, kv, ev); return; }
+            false_++;
+            ev.push_back(Event{FALSE_MATCH, 0, 0, Scalar()});
+            reseed();
+            return;
+        }
+        if (k1 == k2) {                                               // the rule of one key: (sigma1 - eps sigma2) k'' = eps d2 - d1, the divisor +-2 or 0
+            bool tried = false;
+            for (int eps = 1; eps >= -1; eps -= 2) {
+                const int den = s1 - eps * s2;
+                if (!den) continue;
+                tried = true;
+                const i128 num = eps * d2 - d1;
+                if (num & 1) continue;                                // (no integer solves it: mod n it lies far outside the interval)
+                if (verify(k1, num / den, &kv)) { found(k1, kv, ev); return; }
+            }
+            if (tried) { false_++; ev.push_back(Event{FALSE_MATCH, 0, 0, Scalar()}); }
+            reseed();
+            return;
+        }
+        adj_[k1].push_back((uint32_t)links_.size());
+        adj_[k2].push_back((uint32_t)links_.size());
+        links_.push_back(Link{k1, k2, s1, s2, d1, d2, true});
+        kept_++; live_links_++;
+        ev.push_back(Event{LINK, k1, k2, Scalar()});
+        reseed();
+    }
     struct Link { uint32_t j, k; int s1, s2; i128 d1, d2; bool alive; };     // sigma1 k''_j + d1 = +-(sigma2 k''_k + d2)
     static int sigma(uint32_t owner) { return !owner ? 0 : owner & OWNER_NEG ? -1 : 1; }
     // k'' in [-floor(W/2), ceil(W/2)) and (a + floor(W/2) + k'')*G == P_k
@@ -207,8 +222,9 @@ private:
     uint32_t solved_ = 0;
 };
 
-// one scripted record into the table, its event lines printed; false: the record does not parse
-bool scripted_record(SymListTable &tab, size_t n_keys, const std::string &rec)
+// one scripted record into the table, its event lines printed; false: the record does not parse.  stored (-selftest kangaroo-dpkeys sym): the fields of the
+// S, item in front of the record -- tag, d, kangaroo, owner word -- and the record is judged against that entry as a pair
+bool scripted_record(SymListTable &tab, size_t n_keys, const std::string &rec, const std::vector<std::string> *stored = nullptr)
 {
     const std::vector<std::string> f = split_commas(rec);
     if (f.size() != 4 || f[0].empty() || !strchr("TWNDC", f[0][0])) return false;
@@ -226,7 +242,15 @@ bool scripted_record(SymListTable &tab, size_t n_keys, const std::string &rec)
     uint8_t xb[32];
     hs::fe_to_le(x, xb);
     std::vector<SymListTable::Event> ev;
-    tab.add(xb, ((u128)dd.l[1] << 64) | dd.l[0], (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, key, ev);
+    if (stored) {
+        Scalar tag, ed;
+        if (stored->size() != 5 || t == 'D' || t == 'C' || !hs::fe_from_hex(tag, (*stored)[1]) || tag.l[1] || tag.l[2] || tag.l[3] || !hs::fe_from_hex(ed, (*stored)[2]) || ed.l[2] || ed.l[3]) return false;
+        if (x.l[0] != tag.l[0]) { fprintf(stderr, "the record does not share the tag of the stored entry it is paired with\n"); return false; }
+        const uint32_t owner = (uint32_t)strtoul((*stored)[4].c_str(), nullptr, 10);
+        if (!tab.owner_fits(owner)) { fprintf(stderr, "the table is damaged: an entry names owner %u, the list has %zu keys\n", owner, n_keys); return false; }
+        tab.add_pair((i128)(((u128)ed.l[1] << 64) | ed.l[0]), (uint32_t)strtoul((*stored)[3].c_str(), nullptr, 10), owner, ((u128)dd.l[1] << 64) | dd.l[0],
+                     (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, key, ev);
+    } else tab.add(xb, ((u128)dd.l[1] << 64) | dd.l[0], (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, key, ev);
     for (const SymListTable::Event &e : ev) switch (e.what) {
         case SymListTable::NEW: printf("new\n"); break;
         case SymListTable::REPEAT: printf("repeat\n"); break;
@@ -264,6 +288,26 @@ int kangaroo_symlist_selftest(const std::vector<std::string> &a)
     SymListTable tab(lo, W, pubs);
     presolve_scripted(tab, pubs);
     for (size_t i = 3; i < a.size(); i++) if (!scripted_record(tab, pubs.size(), a[i])) return 2;
+    print_summary(tab);
+    return 0;
+}
+
+// -selftest kangaroo-dpkeys sym ...: the symmetric walk's part of -selftest kangaroo-dpkeys (host_kangaroo_multi.cpp describes the items); an owner word is
+// decimal, bit 31 for NEG
+int kangaroo_dpkeys_sym_selftest(const std::vector<std::string> &a)
+{
+    if (a.size() < 3) return 2;
+    Scalar lo, hi; u128 W;
+    std::vector<Affine> pubs;
+    if (!parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
+    SymListTable tab(lo, W, pubs);
+    presolve_scripted(tab, pubs);
+    for (size_t i = 3; i < a.size(); i++) {
+        if (a[i].compare(0, 2, "S,") != 0) { if (!scripted_record(tab, pubs.size(), a[i])) return 2; continue; }
+        if (i + 1 >= a.size()) return 2;                              // a stored entry without its record
+        const std::vector<std::string> s = split_commas(a[i]);
+        if (!scripted_record(tab, pubs.size(), a[++i], &s)) return 2;
+    }
     print_summary(tab);
     return 0;
 }
@@ -342,7 +386,8 @@ struct SymListMode : ListSearch<SymListTable> {
     {
         const Plan &pl = pro->pl;
         if (bsgs_kangaroo_setup_sym_keys(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup_sym_keys";
-        return bsgs_kangaroo_set_keys(dev, qxy.data(), L) == BSGS_OK ? nullptr : "bsgs_kangaroo_set_keys";
+        if (bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) return "bsgs_kangaroo_set_keys";
+        return begin_table(dev);
     }
     void add_record(const bsgs_kangaroo_record &r, uint32_t kid, std::vector<SymListTable::Event> &ev) override
     {
@@ -350,6 +395,13 @@ struct SymListMode : ListSearch<SymListTable> {
         u128 d;
         memcpy(&d, r.d, 16);
         table->add(r.x, d, kid, r.flags, r.reserved, ev);
+    }
+    void add_pair_record(const bsgs_kangaroo_record &st, const bsgs_kangaroo_record &r, uint32_t kid, std::vector<SymListTable::Event> &ev) override
+    {
+        if ((r.flags & BSGS_KANGAROO_WILD) && r.reserved >= L) return;                                           // (as above)
+        u128 d; i128 ed;
+        memcpy(&d, r.d, 16); memcpy(&ed, st.d, 16);
+        table->add_pair(ed, st.kangaroo, st.flags, d, kid, r.flags, r.reserved, ev);
     }
     // (verify_q stays null: the engines hold the key list)  the owner word as the verification's flags: WILD | NEG | k << 8
     uint32_t entry_flags(uint32_t owner) const override

@@ -139,6 +139,10 @@ int selftest(int argc, char **argv)
             return kangaroo_work_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-table-roundtrip") {                    // the table through a work file in the middle of a record stream
             return kangaroo_roundtrip_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-dpkeys-plan") {                        // the plan of -kdpkeys from the range width and the list's length (no GPU)
+            return kangaroo_dpkeys_plan_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-dpkeys") {                             // the hand-back rule of -kdpkeys on scripted records and pairs (no GPU)
+            return kangaroo_dpkeys_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-dpdev-plan") {                         // the plan of -kdpdev from the range width (no GPU)
             return kangaroo_dpdev_plan_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-dpdev") {                              // the hand-back rule of -kdpdev on scripted records and pairs (no GPU)

@@ -33,6 +33,7 @@ NATIVE_SYMBOLS = [
     "bsgs_kangaroo_tames_gen_begin", "bsgs_kangaroo_run_tames_gen", "bsgs_kangaroo_tames_gen_insert", "bsgs_kangaroo_tames_gen_read", "bsgs_kangaroo_tames_gen_end",
     "bsgs_kangaroo_tames_gen_load", "bsgs_kangaroo_tames_gen_read_sorted",
     "bsgs_kangaroo_dptable_begin", "bsgs_kangaroo_run_dptable", "bsgs_kangaroo_dptable_insert", "bsgs_kangaroo_dptable_load", "bsgs_kangaroo_dptable_read", "bsgs_kangaroo_dptable_end",
+    "bsgs_kangaroo_dptable_begin_keys", "bsgs_kangaroo_run_dptable_keys", "bsgs_kangaroo_dptable_insert_keys",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
@@ -80,6 +81,7 @@ KANGAROO_JUMPS, KANGAROO_WILD, KANGAROO_DEAD = 64, 1, 0x80000000
 KANGAROO_NEG, KANGAROO_CYCLE = 2, 4                # the symmetric walk (kangaroo_setup_sym)
 KANGAROO_GEN_DEAD, KANGAROO_GEN_DUPLICATE, KANGAROO_GEN_TAG_ZERO, KANGAROO_GEN_FULL = range(4)   # why the growing tame table hands a record back
 KANGAROO_DPT_DEAD, KANGAROO_DPT_DUPLICATE, KANGAROO_DPT_TAG_ZERO, KANGAROO_DPT_FULL, KANGAROO_DPT_STORED = range(5)   # the distinguished-point table's hand-backs
+KANGAROO_DPT_KEY_SHIFT = 8   # the table for a key list: a hand-back's `reserved` = reason | key << 8; an entry's owner: 0 tame, 1 + key wild, bit 31 NEG
 KANGAROO_KEY_SHIFT, KANGAROO_MAX_KEYS = 8, 65535   # many keys in one herd (kangaroo_set_keys): a wild kangaroo's key index, 16 bits of its flags
 
 _lib = None
@@ -216,6 +218,11 @@ def lib():
             "bsgs_kangaroo_dptable_load": [vp, vp, C.c_uint64] + [C.POINTER(C.c_uint64)] * 5,
             "bsgs_kangaroo_dptable_read": [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)],
             "bsgs_kangaroo_dptable_end": [vp],
+            "bsgs_kangaroo_dptable_begin_keys": [vp, C.c_uint64],
+            "bsgs_kangaroo_run_dptable_keys": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
+            "bsgs_kangaroo_dptable_insert_keys": [vp, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32),
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
             "bsgs_kangaroo_run_tames_keys": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_float)],
         }
@@ -975,6 +982,56 @@ class Device:
 
     def kangaroo_dptable_end(self):
         _chk(self.L.bsgs_kangaroo_dptable_end(self.h))
+
+    # ---- the distinguished-point table for a key list (include/bsgs_hip.h "Kangaroo, distinguished-point table for a key list")
+    @staticmethod
+    def _keys_handed_back(recs, n):
+        """a hand-back of the keyed table: the stored half of a pair has reason KANGAROO_DPT_STORED, flags = its owner word and key None; a record of the
+        walk has its reason and the key it named"""
+        out = []
+        for r in recs[:n]:
+            stored = r.reserved == KANGAROO_DPT_STORED
+            out.append({"x": int.from_bytes(bytes(r.x), "little"), "d": int.from_bytes(bytes(r.d), "little"), "kangaroo": r.kangaroo, "flags": r.flags, "step": r.step,
+                        "reason": KANGAROO_DPT_STORED if stored else r.reserved & ((1 << KANGAROO_DPT_KEY_SHIFT) - 1),
+                        "key": None if stored else r.reserved >> KANGAROO_DPT_KEY_SHIFT})
+        return out
+
+    def kangaroo_dptable_begin_keys(self, capacity):
+        """allocates the keyed table for `capacity` entries under a herd of kangaroo_setup / kangaroo_setup_sym_keys that has a key list"""
+        _chk(self.L.bsgs_kangaroo_dptable_begin_keys(self.h, capacity))
+
+    def kangaroo_run_dptable_keys(self, steps, max_recs=None, raw=False):
+        """kangaroo_run_dptable on the keyed table: (hand-backs, n_seen, n_entries, dropped, kernel ms); a hand-back has "reason" and "key"; raw: the bytes
+        of the hand-backs (`reserved` = reason | key << KANGAROO_DPT_KEY_SHIFT)"""
+        cap = 2 * self._kang_cap if max_recs is None else max_recs
+        n, seen, entries, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        if raw:
+            recs, buf = self._raw_records_out(cap)
+            _chk(self.L.bsgs_kangaroo_run_dptable_keys(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
+            return buf.raw[:64 * n.value], seen.value, entries.value, dropped.value, ms.value
+        recs = (KangarooRecord * max(1, cap))()
+        _chk(self.L.bsgs_kangaroo_run_dptable_keys(self.h, steps, recs, cap, C.byref(n), C.byref(seen), C.byref(entries), C.byref(dropped), C.byref(ms)))
+        return self._keys_handed_back(recs, n.value), seen.value, entries.value, dropped.value, ms.value
+
+    def kangaroo_dptable_insert_keys(self, records, max_recs=None, raw=False):
+        """the keyed insert and the resolve alone on records of the caller's, (tag or x, d, flags, kangaroo, reserved) each: (hand-backs, n_entries,
+        dropped); raw: records = the bytes of 64-byte records, and the hand-backs come as bytes too"""
+        cap = 2 * self._kang_cap if max_recs is None else max_recs
+        n, entries, dropped = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        if raw:
+            arr, m, keep = self._raw_records_in(records)
+            out, buf = self._raw_records_out(cap)
+            _chk(self.L.bsgs_kangaroo_dptable_insert_keys(self.h, arr, m, out, cap, C.byref(n), C.byref(entries), C.byref(dropped)))
+            return buf.raw[:64 * n.value], entries.value, dropped.value
+        m = len(records)
+        arr = (KangarooRecord * max(1, m))()
+        for k, (x, d, fl, kang, res) in enumerate(records):
+            arr[k].x[:] = le32(x)
+            arr[k].d[:] = (d % (1 << 128)).to_bytes(16, "little")
+            arr[k].flags, arr[k].kangaroo, arr[k].reserved = fl, kang, res
+        out = (KangarooRecord * max(1, cap))()
+        _chk(self.L.bsgs_kangaroo_dptable_insert_keys(self.h, arr, m, out, cap, C.byref(n), C.byref(entries), C.byref(dropped)))
+        return self._keys_handed_back(out, n.value), entries.value, dropped.value
 
     def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):
         """start points on the GPU: kangaroo idx[k] (first + k without idx) := (d*G or Q + d*G, d, flags[k]) for d = offsets[k] (a signed integer) and

@@ -2,7 +2,7 @@
 """Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
-    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--dptable N] [--no-vgprs] [--out FILE]
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--dptable N [--keys]] [--no-vgprs] [--out FILE]
     tools/kangaroo_rate.py --tamesload N | --tamessort N [--reps 3] [--out FILE]
 
 --sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch); with --keys
@@ -19,7 +19,10 @@ process: the difference of their kernel times is the insert.  Plain walk, or wit
 --dptable N begins a distinguished-point table of capacity N in device memory (bsgs_kangaroo_dptable_begin) under a herd of pairwise different starts, half
 tame and half wild (seeded on the GPU), and times bsgs_kangaroo_run_dptable and bsgs_kangaroo_run in turn, launch by launch, in one process: the difference
 of their kernel times is insert + resolve.  Plain walk, or with --sym the symmetric one: the search of -kdpdev.  Choose --steps and --dp so that a launch
-writes at most 2^22 records (a full herd at --dp 7: --steps 64).
+writes at most 2^22 records (a full herd at --dp 7: --steps 64).  With --keys the table is the one for a key list (bsgs_kangaroo_dptable_begin_keys,
+bsgs_kangaroo_run_dptable_keys: the search of -infile -kdpkeys) under a herd that serves 16 keys -- that of bsgs_kangaroo_setup with a key list, or with
+--sym that of bsgs_kangaroo_setup_sym_keys -- seeded by bsgs_kangaroo_seed_keys, the wild half dealt out over the keys: the walk alone and walk + keyed
+insert + resolve, alternating in one process.
 
 --tamesload N times bsgs_kangaroo_tames_gen_load of N synthetic entries (pairwise different tags, 24 bytes each from pageable host memory) into a fresh growing
 table of capacity N, --reps times.  --tamessort N loads such a table once and times bsgs_kangaroo_tames_gen_read_sorted of all N entries (harvest, radix sort,
@@ -137,12 +140,12 @@ def main():
     ap.add_argument("--no-vgprs", action="store_true", help="do not compile the walk's unit for its VGPR count")
     ap.add_argument("--out")
     a = ap.parse_args()
-    if a.keys and not a.sym:
-        ap.error("--keys goes with --sym")
+    if a.keys and not a.sym and not a.dptable:
+        ap.error("--keys goes with --sym, or with --dptable")
     if a.tamesgen and (a.keys or a.tames):
         ap.error("--tamesgen goes with the plain walk or --sym alone")
-    if a.dptable and (a.keys or a.tames or a.tamesgen):
-        ap.error("--dptable goes with the plain walk or --sym alone")
+    if a.dptable and (a.tames or a.tamesgen):
+        ap.error("--dptable goes with the plain walk or --sym, alone or with --keys")
     if a.tamesload or a.tamessort:
         return table_legs(a)
     dev = pybsgs.Device(0)
@@ -154,7 +157,7 @@ def main():
     if a.sym:
         # scalars without additive structure: multiples of one constant satisfy s_a + s_b = s_c + s_d all over and would fill the walk with fruitless cycles
         scal = [splitmix64(j)[1] % (1 << 62) + 1 for j in range(a.jumps)]
-        (dev.kangaroo_setup_sym_keys if a.keys else dev.kangaroo_setup_sym)([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
+        (dev.kangaroo_setup_sym_keys if a.keys else dev.kangaroo_setup_sym)([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)      # (--keys: the list's herd)
     else:
         dev.kangaroo_setup([mul(s) for s in scal], scal, a.dp, n, a.per_thread, 1 << 22)
     distinct = 65536
@@ -221,14 +224,20 @@ def main():
         d[:, 1] &= np.uint64((1 << 36) - 1)                          # offsets below 2^100, pairwise different but for a 2^-62 chance
         flags = (C.c_uint32 * n)(*([0] * (n // 2) + [pybsgs.KANGAROO_WILD] * (n - n // 2)))
         q = mul(0xD15C0 << 70)
-        pybsgs._chk(L.bsgs_kangaroo_seed(dev.h, pybsgs.le32(q[0]) + pybsgs.le32(q[1]), None, 0, n, d.tobytes(), flags, None, None))
+        if a.keys:                                                    # sixteen keys, the wild half dealt out over them
+            dev.kangaroo_set_keys([add(q, mul(k + 1)) for k in range(16)])
+            key = (C.c_uint32 * n)(*([0] * (n // 2) + [k & 15 for k in range(n - n // 2)]))
+            pybsgs._chk(L.bsgs_kangaroo_seed_keys(dev.h, None, 0, n, d.tobytes(), flags, key, None, None))
+        else:
+            pybsgs._chk(L.bsgs_kangaroo_seed(dev.h, pybsgs.le32(q[0]) + pybsgs.le32(q[1]), None, 0, n, d.tobytes(), flags, None, None))
         t0 = time.perf_counter()
-        pybsgs._chk(L.bsgs_kangaroo_dptable_begin(dev.h, a.dptable))
+        pybsgs._chk((L.bsgs_kangaroo_dptable_begin_keys if a.keys else L.bsgs_kangaroo_dptable_begin)(dev.h, a.dptable))
         begin_s = time.perf_counter() - t0
         seen, n_entries = C.c_uint64(), C.c_uint64()
+        run_dpt = L.bsgs_kangaroo_run_dptable_keys if a.keys else L.bsgs_kangaroo_run_dptable
 
         def launch_dpt():
-            pybsgs._chk(L.bsgs_kangaroo_run_dptable(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(n_entries), C.byref(dropped), C.byref(ms)))
+            pybsgs._chk(run_dpt(dev.h, a.steps, recs, 1 << 22, C.byref(cnt), C.byref(seen), C.byref(n_entries), C.byref(dropped), C.byref(ms)))
             return ms.value, seen.value, cnt.value
 
         for _ in range(a.warmup):
@@ -243,7 +252,8 @@ def main():
             back += m
             dr += dropped.value
         ins = (sum(both) - sum(plain)) / len(both)
-        res = {"what": "kangaroo walk with the distinguished-point table in device memory, one engine, full herd, half tame half wild" + (", symmetric walk" if a.sym else ""),
+        res = {"what": "kangaroo walk with the distinguished-point table in device memory, one engine, full herd, half tame half wild" + (", symmetric walk" if a.sym else "") +
+               (", the table for a key list (16 keys)" if a.keys else ""),
                "gpu": dev.name(), "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp, "launches": a.launches, "capacity": a.dptable,
                "slots": 1 << max(7, (2 * (a.dptable + (1 << 22)) - 1).bit_length()), "begin_s": begin_s,
                "ms_per_launch_walk": sum(plain) / len(plain), "ms_per_launch_walk_insert_resolve": sum(both) / len(both), "ms_insert_resolve": ins,
