@@ -7,9 +7,10 @@
 // -ksym runs the symmetric walk (the negation map; include/bsgs_hip.h "Kangaroo, symmetric walk"): offsets counted from the middle of the range, R jump points
 // (-kjumps) of mean -kjumpscale * N_k sqrt(W) / 4, the collision rule with signs, cycles counted, a version-2 work file; -selftest kangaroo-sym / kangaroo-sym-roundtrip.
 // -kdpdev keeps the distinguished points in device memory (include/bsgs_hip.h "Kangaroo, distinguished-point table in device memory"): the launch inserts and
-// pairs them there, the collector judges the handed-back pairs by the table's own rule, the device table is read where the herd is downloaded for a save and
-// loaded at -wl; the plan is a low dp and the full herd; -selftest kangaroo-dpdev / kangaroo-dpdev-plan.
-#include "host_kangaroo_run.h"
+// pairs them there, the device table is read where the herd is downloaded for a save and loaded at -wl -- all of that is DevDpTable's
+// (host_kangaroo_dptable.h), KeyMode's member dpt; KeyMode says which type words are legal and judges the handed-back pairs by the table's own rule; the plan is
+// a low dp and the full herd; -selftest kangaroo-dpdev (through DevDpTable::take) / kangaroo-dpdev-plan.
+#include "host_kangaroo_dptable.h"
 
 #include <unordered_map>
 
@@ -159,20 +160,31 @@ bool parse_range_pub(const std::string &pk, const std::string &pke, const std::s
     return true;
 }
 // one scripted record (T|W|D,<x hex>,<d hex>,<kangaroo>; sym: also N, a wild kangaroo with NEG, and C, a cycle's dead record) into the table: prints the
-// verdict line of -selftest kangaroo
-bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = false)
+// verdict line of -selftest kangaroo.  dpt (-selftest kangaroo-dpdev): the record goes through DevDpTable::take as the device would hand it back -- paired: as
+// the duplicate behind the stored half taken before it, never a dead record -- and is judged as take() names it
+bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = false, DevDpTable *dpt = nullptr, bool paired = false)
 {
     const std::vector<std::string> f = split_commas(rec);
-    if (f.size() != 4 || f[0].size() != 1 || !strchr(sym ? "TWDNC" : "TWD", f[0][0])) return false;
+    if (f.size() != 4 || f[0].size() != 1 || !strchr(paired ? (sym ? "TWN" : "TW") : (sym ? "TWDNC" : "TWD"), f[0][0])) return false;
     Scalar x;
     u128 d;
     if (!hs::fe_from_hex(x, f[1]) || !parse_hex128(f[2], d)) return false;
-    uint8_t xb[32];
-    hs::fe_to_le(x, xb);
-    const uint32_t flags = f[0] == "W" ? BSGS_KANGAROO_WILD : f[0] == "D" ? BSGS_KANGAROO_DEAD : f[0] == "N" ? BSGS_KANGAROO_WILD | BSGS_KANGAROO_NEG :
-                           f[0] == "C" ? BSGS_KANGAROO_DEAD | BSGS_KANGAROO_CYCLE : 0u;
+    bsgs_kangaroo_record r;
+    memset(&r, 0, sizeof r);
+    hs::fe_to_le(x, r.x);
+    memcpy(r.d, &d, 16);
+    r.kangaroo = (uint32_t)strtoul(f[3].c_str(), nullptr, 10);
+    r.flags = f[0] == "W" ? BSGS_KANGAROO_WILD : f[0] == "D" ? BSGS_KANGAROO_DEAD : f[0] == "N" ? BSGS_KANGAROO_WILD | BSGS_KANGAROO_NEG :
+              f[0] == "C" ? BSGS_KANGAROO_DEAD | BSGS_KANGAROO_CYCLE : 0u;
+    DevDpTable off;
+    const DevDpTable::Taken t = (dpt ? dpt : &off)->take_scripted(r, 0, paired);
     Scalar key;
-    switch (tab.add(xb, d, (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, &key)) {
+    KangarooTable::Verdict v;
+    u128 ed;
+    if (t.kind == DevDpTable::PAIR) { memcpy(&ed, t.stored->d, 16); v = tab.add_pair(ed, t.stored->kangaroo, t.stored->flags, d, r.kangaroo, r.flags, &key); }
+    else if (t.kind == DevDpTable::ALONE || t.kind == DevDpTable::NOT_MINE) v = tab.add(r.x, d, r.kangaroo, r.flags, &key);
+    else return false;
+    switch (v) {
     case KangarooTable::NEW: printf("new\n"); break;
     case KangarooTable::FOUND: printf("found %s\n", hs::fe_to_hex(key).c_str()); break;
     case KangarooTable::RESEED: printf("reseed %s\n", f[3].c_str()); break;
@@ -185,83 +197,39 @@ bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = fals
 
 // -selftest kangaroo <pk hex> <pke hex> <pubkey> <record>...  record = T|W|D,<x hex>,<d hex: 128-bit two's complement>,<kangaroo> (D: a dead record).
 // Prints one line per record: "new", "found <key hex>", "reseed <kangaroo>", "false", "repeat"; then "summary <stored> <false matches> <reseeds>".
-int kangaroo_selftest(const std::vector<std::string> &a)
-{
-    if (a.size() < 3) return 2;
-    Scalar lo, hi; Affine P; u128 W;
-    if (!parse_range_pub(a[0], a[1], a[2], lo, hi, P, W)) return 2;
-    KangarooTable tab(lo, W, P);
-    for (size_t i = 3; i < a.size(); i++) if (!scripted_record(tab, a[i])) return 2;
-    printf("summary %zu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds());
-    return 0;
-}
-
-// -selftest kangaroo-sym <pk hex> <pke hex> <pubkey> <record>...: as -selftest kangaroo through the symmetric table (record types T, W, N, D, C); the summary
-// line is "summary <stored> <false matches> <reseeds> <cycles>".
-int kangaroo_sym_selftest(const std::vector<std::string> &a)
-{
-    if (a.size() < 3) return 2;
-    Scalar lo, hi; Affine P; u128 W;
-    if (!parse_range_pub(a[0], a[1], a[2], lo, hi, P, W)) return 2;
-    KangarooTable tab(lo, W, P, true);
-    for (size_t i = 3; i < a.size(); i++) if (!scripted_record(tab, a[i], true)) return 2;
-    printf("summary %zu %llu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds(), (unsigned long long)tab.cycles());
-    return 0;
-}
-
-// -selftest kangaroo-dpdev [sym] <pk hex> <pke hex> <pubkey> <item>...: the hand-back rule of -kdpdev without a GPU.  An item is a scripted record as
-// -selftest kangaroo (sym: kangaroo-sym) takes it -- what the device hands back alone: DEAD, tag 0, a full table -- and goes through the host's own map; or
+// -selftest kangaroo-sym: the same through the symmetric table (record types T, W, N, D, C); the summary line is "summary <stored> <false matches> <reseeds> <cycles>".
+// -selftest kangaroo-dpdev [sym] <pk hex> <pke hex> <pubkey> <item>...: the hand-back rule of -kdpdev without a GPU, every item through DevDpTable::take.  An
+// item is a scripted record as above -- what the device hands back alone: DEAD, tag 0, a full table -- and goes through the host's own map; or
 // S,<tag hex>,<d hex>,<kangaroo>,<type> followed by its record: a duplicate, judged against the stored entry it came with.  The same verdict and summary lines.
-int kangaroo_dpdev_selftest(const std::vector<std::string> &args)
+static int table_selftest(const std::vector<std::string> &a, bool sym, bool dpdev)
 {
-    std::vector<std::string> a(args);
-    const bool sym = !a.empty() && a[0] == "sym";
-    if (sym) a.erase(a.begin());
     if (a.size() < 3) return 2;
     Scalar lo, hi; Affine P; u128 W;
     if (!parse_range_pub(a[0], a[1], a[2], lo, hi, P, W)) return 2;
     KangarooTable tab(lo, W, P, sym);
-    for (size_t i = 3; i < a.size(); i++) {
-        if (a[i].compare(0, 2, "S,") != 0) { if (!scripted_record(tab, a[i], sym)) return 2; continue; }
-        const std::vector<std::string> s = split_commas(a[i]);
-        if (s.size() != 5 || i + 1 >= a.size()) return 2;
-        const std::vector<std::string> f = split_commas(a[++i]);
-        u128 tag, ed, d;
-        Scalar x;
-        if (f.size() != 4 || f[0].size() != 1 || !strchr(sym ? "TWN" : "TW", f[0][0]) || !parse_hex128(s[1], tag) || (tag >> 64) || !parse_hex128(s[2], ed) ||
-            !hs::fe_from_hex(x, f[1]) || !parse_hex128(f[2], d)) return 2;
-        const uint32_t type = (uint32_t)strtoul(s[4].c_str(), nullptr, 10);
-        if (type > 1u && !(sym && type == 3u)) return 2;
-        if (x.l[0] != (uint64_t)tag) { fprintf(stderr, "the record does not share the tag of the stored entry it is paired with\n"); return 2; }
-        const uint32_t flags = f[0] == "W" ? BSGS_KANGAROO_WILD : f[0] == "N" ? BSGS_KANGAROO_WILD | BSGS_KANGAROO_NEG : 0u;
-        Scalar key;
-        switch (tab.add_pair(ed, (uint32_t)strtoul(s[3].c_str(), nullptr, 10), type, d, (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, &key)) {
-        case KangarooTable::NEW: return 1;                            // (never: a pair is judged, not stored)
-        case KangarooTable::FOUND: printf("found %s\n", hs::fe_to_hex(key).c_str()); break;
-        case KangarooTable::RESEED: printf("reseed %s\n", f[3].c_str()); break;
-        case KangarooTable::FALSE_MATCH: printf("false\n"); break;
-        case KangarooTable::REPEAT: printf("repeat\n"); break;
-        }
-    }
+    DevDpTable dpt;
+    dpt.on = dpdev;
+    if (!dpt.scripted_items(a, [&](const std::string &rec, bool paired) {
+            return !(paired && dpt.half.flags > 1u && !(sym && dpt.half.flags == 3u)) && scripted_record(tab, rec, sym, &dpt, paired); })) return 2;
     if (sym) printf("summary %zu %llu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds(), (unsigned long long)tab.cycles());
     else printf("summary %zu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds());
     return 0;
 }
+int kangaroo_selftest(const std::vector<std::string> &a) { return table_selftest(a, false, false); }
+int kangaroo_sym_selftest(const std::vector<std::string> &a) { return table_selftest(a, true, false); }
+int kangaroo_dpdev_selftest(const std::vector<std::string> &a)
+{
+    const bool sym = !a.empty() && a[0] == "sym";
+    return table_selftest(sym ? std::vector<std::string>(a.begin() + 1, a.end()) : a, sym, true);
+}
 
 // -selftest kangaroo-dpdev-plan <pk hex> <pke hex> <CUs> <min launch> <dp or -1> <kn or 0> <kdpn or 0>: the plan of -kdpdev for one engine without a GPU, one line:
-// "plan <dp> <kn> <per thread> <S> <record buffer> <capacity>"
+// "plan <dp> <kn> <per thread> <S> <record buffer> <capacity>" -- that of -kdpkeys (host_kangaroo_multi.cpp) for one open key
 int kangaroo_dpdev_plan_selftest(const std::vector<std::string> &a)
 {
-    if (a.size() != 7) return 2;
-    KangConfig c;
-    c.pk = a[0]; c.pke = a[1];
-    Prologue p(c);
-    const int cus = atoi(a[2].c_str()), dp_arg = atoi(a[4].c_str());
-    const uint64_t capacity = dpdev_capacity(p.sqrtW, strtoull(a[6].c_str(), nullptr, 0));
-    Plan pl = plan_herd(p.sqrtW, 1, cus, dp_arg >= 0 ? dp_arg : (int)dpdev_dp(p.sqrtW, capacity), strtoull(a[5].c_str(), nullptr, 0));
-    plan_launch(pl, p.sqrtW, 0.0, atof(a[3].c_str()), true, dp_arg < 0);
-    printf("plan %u %llu %u %u %u %llu\n", pl.dp, (unsigned long long)pl.kn, pl.G, pl.S, pl.cap, (unsigned long long)capacity);
-    return 0;
+    std::vector<std::string> b(a);
+    b.push_back("1");
+    return a.size() == 7 ? kangaroo_dpkeys_plan_selftest(b) : 2;
 }
 
 // -selftest kangaroo-table-roundtrip <pk hex> <pke hex> <pubkey> <split> <record>...: the first <split> records into a table, the table into a work file
@@ -354,6 +322,14 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
     }
     // -kdpdev: the table of distinguished points of the one-key search, plain and -ksym, in device memory; every refusal before any device is looked for
     if (c.kdpn && !c.kdpdev && !c.kdpkeys) die("-kdpn belongs to -kdpdev or -kdpkeys (the capacity of the table in GPU memory)");
+    // one engine with one table: one -d entry; without -d a run takes every GPU of the machine, here it takes the first
+    auto one_engine = [&c](const std::string &flag) {
+        if (c.devices.find(',') != std::string::npos) die("-kangaroo " + flag + " takes one -d entry (several engines would need one table for all of them)");
+        if (c.devices.empty()) {
+            c.devices = "0";
+            printf("Kangaroo %s: no -d given, one engine on GPU #0\n", flag.c_str());
+        }
+    };
     // -kdpkeys: the same for the list of -infile, plain and -kwalk sym, with an owner per entry
     if (c.kdpkeys) {
         if (c.kdpdev) die("-kangaroo -kdpkeys cannot be combined with -kdpdev (-kdpdev is the table of one key, -kdpkeys that of a key list)");
@@ -361,21 +337,13 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         if (c.infile.empty()) die("-kangaroo -kdpkeys needs -infile (it keeps the table of a key list in GPU memory)");
         if (!c.ktames.empty() || !c.ktamesgen.empty() || !c.ktamesmerge.empty() || c.ktamesdev || !c.ktamesfrom.empty() || c.ktnplan || c.ktn)
             die("-kangaroo -kdpkeys cannot be combined with -ktames, -ktamessym, -ktamesgen or their flags (a tame table is matched or grown by calls of its own)");
-        if (c.devices.find(',') != std::string::npos) die("-kangaroo -kdpkeys takes one -d entry (several engines would need one table for all of them)");
-        if (c.devices.empty()) {
-            c.devices = "0";
-            printf("Kangaroo -kdpkeys: no -d given, one engine on GPU #0\n");
-        }
+        one_engine("-kdpkeys");
     }
     if (c.kdpdev) {
         if (!c.infile.empty()) die("-kangaroo -kdpdev cannot be combined with -infile (the table in GPU memory pairs the records of one key; -kdpkeys keeps the table of a key list there)");
         if (!c.ktames.empty() || !c.ktamesgen.empty() || !c.ktamesmerge.empty())
             die("-kangaroo -kdpdev cannot be combined with -ktames, -ktamessym, -ktamesgen or -ktamesmerge (a tame table is matched or grown by calls of its own)");
-        if (c.devices.find(',') != std::string::npos) die("-kangaroo -kdpdev takes one -d entry (several engines would need one table for all of them)");
-        if (c.devices.empty()) {                                       // without -d a run takes every GPU of the machine: here it takes the first
-            c.devices = "0";
-            printf("Kangaroo -kdpdev: no -d given, one engine on GPU #0\n");
-        }
+        one_engine("-kdpdev");
     }
     // a tame table (host_kangaroo_tames.cpp): made by the plain walk, or with -kwalk sym by the symmetric walk (file version 2); searched with -ktames,
     // a table of the symmetric walk with -ktamessym; never saved; every refusal before any device is looked for
@@ -456,7 +424,7 @@ struct KeyMode : Mode {
     KeyMode(const KangConfig &c, const Affine &P) : c(c), P(P)
     {
         if (c.sym) { version = WORK_VERSION_SYM; min_launch = 2.0 * BSGS_KANGAROO_CYCLE_WINDOW; }      // -ksym: a launch longer than the cycle window
-        if (c.kdpdev) { counts_records = false; bound_launch = true; dp_free = c.dp < 0; }             // -kdpdev: the launch counts, and is kept within the record buffer
+        dpt.enable(c, *this);
     }
     std::string fingerprint(const Prologue &p, const WorkHeader &h) const override { return kangaroo_fingerprint(P, p.lo, p.hi, h); }
     bool before_devices(Prologue &p) override
@@ -470,11 +438,7 @@ struct KeyMode : Mode {
         }
         printf("Kangaroo range [%s, %s], width 2^%.2f\n", hs::fe_to_hex(p.lo).c_str(), hs::fe_to_hex(p.hi).c_str(), std::log2((double)p.W));
         if (c.kdpdev && p.resume && f.engines != 1) die("Recovery file was made with other settings");      // (-kdpdev is one engine with one table)
-        if (c.kdpdev) {                                                // the table in device memory: its capacity, and the dp that fills at most half of it
-            capacity = dpdev_capacity(p.sqrtW, c.kdpn);
-            while (p.resume && capacity < 2 * f.table && capacity < (1ull << 31)) capacity *= 2;      // (a file that holds more than this run would plan for)
-            dp_fixed = c.dp >= 0 ? c.dp : (int)dpdev_dp(p.sqrtW, capacity);
-        }
+        if (c.kdpdev) dp_fixed = dpt.plan(c, p.sqrtW, p.resume ? f.table : 0);
         // -ksym: offsets are counted from the middle of the range, k'' = k - (a + W/2) (include/bsgs_hip.h "Kangaroo, symmetric walk")
         base = c.sym ? hs::sc_add(p.lo, hs::sc_from_u128(p.W / 2)) : p.lo;
         Q = hs::point_add(P, hs::affine_neg(hs::point_mul(hs::G, base)));
@@ -494,19 +458,8 @@ struct KeyMode : Mode {
     {
         table.reset(new KangarooTable(p.lo, p.W, P, c.sym));
         if (p.resume) {
-            if (c.kdpdev) {                                            // the file's entries go to the device once they are verified (resumed()); tag 0 stays here
-                std::vector<uint8_t> own;
-                for (uint64_t i = 0; i < p.wf.h.table; i++) {
-                    const uint8_t *en = &p.wf.table[32 * i];
-                    uint64_t k64; uint32_t type;
-                    memcpy(&k64, en, 8); memcpy(&type, en + 28, 4);
-                    if (type > 1u && !(c.sym && type == 3u)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
-                    std::vector<uint8_t> &to = k64 ? pending : own;
-                    to.insert(to.end(), en, en + 32);
-                }
-                p.wf.table.swap(own);
-                dev_entries = pending.size() / 32;
-            }
+            const bool sym = c.sym;                                    // the type words of a table entry: 0 tame, 1 wild, -ksym: 3 wild with NEG
+            if (c.kdpdev && !dpt.split(p.wf.table, [sym](uint32_t type) { return type <= 1u || (sym && type == 3u); })) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
             if (!table->restore(p.wf.table.data(), p.wf.table.size() / 32, p.wf.h.false_matches, p.wf.h.reseeds)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
             std::vector<uint8_t>().swap(p.wf.table);
             table->set_cycles(p.wf.h.cycles);
@@ -562,52 +515,16 @@ struct KeyMode : Mode {
         const Plan &pl = pro->pl;
         if ((c.sym ? bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)
                    : bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)) != BSGS_OK) return "bsgs_kangaroo_setup";
-        if (c.kdpdev && bsgs_kangaroo_dptable_begin(dev, capacity) != BSGS_OK) return "bsgs_kangaroo_dptable_begin";
-        return nullptr;
+        return dpt.begin(dev);
     }
-    // -kdpdev: the walk, the insert and the pairing in device memory; only the hand-backs reach the collector, and the DP count is the walk's
+    // -kdpdev: the launch, the load at -wl and the read for a save are the device table's
     int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &sh) override
     {
-        if (!c.kdpdev) return Mode::launch(dev, e, steps, recs, cap, n, dropped, sh);
-        uint64_t seen = 0, entries = 0;
-        const int rc = bsgs_kangaroo_run_dptable(dev, steps, recs, cap, n, &seen, &entries, dropped, nullptr);
-        if (rc != BSGS_OK) return rc;
-        uint64_t dead = 0;
-        for (uint32_t i = 0; i < *n; i++) dead += recs[i].reserved != BSGS_KANGAROO_DPT_STORED && (recs[i].flags & BSGS_KANGAROO_DEAD);
-        sh.dps += seen - std::min(seen, dead);
-        dev_entries = entries;
-        return rc;
+        return dpt.on ? dpt.launch(dev, steps, recs, cap, n, dropped, sh) : Mode::launch(dev, e, steps, recs, cap, n, dropped, sh);
     }
-    // -kdpdev -wl: the file's entries, verified, into the device table; a tag that occurs twice or finds no slot: the section does not load
-    std::string resumed(bsgs_dev *dev, uint32_t e, Shared &sh) override
-    {
-        (void)e; (void)sh;
-        if (!c.kdpdev || pending.empty()) return "";
-        uint64_t stored = 0, dup = 0, zero = 0, full = 0, entries = 0;
-        const auto ts = Clock::now();
-        if (bsgs_kangaroo_dptable_load(dev, (const bsgs_kangaroo_dp_entry *)pending.data(), pending.size() / 32, &stored, &dup, &zero, &full, &entries) != BSGS_OK)
-            return std::string("bsgs_kangaroo_dptable_load: ") + bsgs_last_error();
-        if (dup || full || zero) return "-kangaroo -wl: the table section of " + pro->wl_path + " does not load";
-        printf("[startup] %-44s %.3fs\n", ("table (GPU memory), " + std::to_string(entries) + " entries").c_str(), since(ts));
-        dev_entries = entries;
-        std::vector<uint8_t>().swap(pending);
-        return "";
-    }
-    // -kdpdev: the device table as it stands, for save()
-    std::string fetch(bsgs_dev *dev, uint32_t e, Shared &sh) override
-    {
-        (void)e; (void)sh;
-        if (!c.kdpdev) return "";
-        uint64_t n = 0;
-        if (bsgs_kangaroo_dptable_read(dev, nullptr, 0, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();      // the count alone
-        std::vector<uint8_t> got(32 * n);
-        if (n && bsgs_kangaroo_dptable_read(dev, (bsgs_kangaroo_dp_entry *)got.data(), n, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();
-        if (32 * n != got.size()) return "bsgs_kangaroo_dptable_read: the table changed between the count and the read";
-        std::lock_guard<std::mutex> lk(dev_m);
-        dev_table.swap(got);
-        return "";
-    }
-    size_t table_size() const { return table->size() + (size_t)dev_entries.load(); }      // "in the table": the host's entries and the device's
+    std::string resumed(bsgs_dev *dev, uint32_t, Shared &) override { return dpt.resumed(dev, pro->wl_path); }
+    std::string fetch(bsgs_dev *dev, uint32_t, Shared &) override { return dpt.fetch(dev); }
+    size_t table_size() const { return table->size() + (size_t)dpt.entries.load(); }      // "in the table": the host's entries and the device's
     // (a whole herd from the host's comb was computed in prepare() and is uploaded by the driver: the comb is asked for lists only)
     const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) override
     {
@@ -639,14 +556,13 @@ struct KeyMode : Mode {
         Scalar k;
         const uint32_t kid = (uint32_t)(e * pro->pl.kn + r.kangaroo);
         KangarooTable::Verdict v;
-        if (c.kdpdev && r.reserved == BSGS_KANGAROO_DPT_STORED) { stored = r; have_stored = true; return true; }      // the entry the next record met
-        if (c.kdpdev && r.reserved == BSGS_KANGAROO_DPT_DUPLICATE) {
-            if (!have_stored) return true;                             // (never: the device does not split a pair)
-            have_stored = false;
-            u128 ed;
-            memcpy(&ed, stored.d, 16);
-            v = table->add_pair(ed, stored.kangaroo, stored.flags, d, kid, r.flags, &k);
-        } else v = table->add(r.x, d, kid, r.flags, &k);               // -kdpdev: DEAD, tag 0, a full device table -- the host's own map, as without the flag
+        const DevDpTable::Taken t = dpt.take(r);
+        u128 ed;
+        switch (t.kind) {
+        case DevDpTable::STORED_HALF: case DevDpTable::ORPHAN: return true;
+        case DevDpTable::PAIR: memcpy(&ed, t.stored->d, 16); v = table->add_pair(ed, t.stored->kangaroo, t.stored->flags, d, kid, r.flags, &k); break;
+        default: v = table->add(r.x, d, kid, r.flags, &k);             // no -kdpdev, or what the device hands back alone: the host's own map
+        }
         if (v == KangarooTable::FOUND) { key = k; found = true; sh.stop = true; return false; }
         if (v == KangarooTable::RESEED) sh.push_reseed(e, r.kangaroo);
         return true;
@@ -661,11 +577,8 @@ struct KeyMode : Mode {
     }
     const WorkKeys *save(WorkHeader &h, std::vector<uint8_t> &entries) override
     {
-        std::lock_guard<std::mutex> lk(dev_m);
-        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.table = table->size() + dev_table.size() / 32; h.cycles = table->cycles();
-        entries.swap(dev_table);                                       // -kdpdev: what fetch() read when the herds were downloaded -- moved, not copied: every save
-        std::vector<uint8_t>().swap(dev_table);                        // follows a fetch() of its own
-        entries.reserve(entries.size() + 32 * table->size());
+        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.cycles = table->cycles();
+        dpt.save(h, entries, table->size());                           // -kdpdev: the device's entries first
         table->write_entries(entries);
         return nullptr;
     }
@@ -683,13 +596,7 @@ struct KeyMode : Mode {
     bool cpuseed = false;
     std::unique_ptr<Comb> comb;
     std::vector<std::vector<i128>> off0;
-    // -kdpdev
-    uint64_t capacity = 0;                         // of the device table
-    std::atomic<uint64_t> dev_entries{0};          // entries in it after the last launch
-    std::vector<uint8_t> pending, dev_table;       // -wl: the file's entries on their way to the device; the device table as fetch() read it
-    std::mutex dev_m;
-    bsgs_kangaroo_record stored;                   // the first record of a handed-back pair, until its record comes
-    bool have_stored = false;
+    DevDpTable dpt;                                // -kdpdev
 };
 }  // namespace
 
@@ -706,12 +613,8 @@ int kangaroo_main(int argc, char **argv)
     p.complete(c, mode);
     const Plan &pl = p.pl;
     printf("Expected steps: 2^%.2f (2 sqrt(W) + DP overhead), expected DPs 2^%.2f\n", std::log2(pl.expected), std::log2(2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) + 1.0));
-    if (c.kdpdev) {
-        uint64_t slots = 128;
-        while (slots < 2 * (mode.capacity + pl.cap)) slots *= 2;
-        printf("Kangaroo: distinguished points stay in GPU memory (-kdpdev): table of %llu entries, %llu slots, %.2f GiB; hand-backs only cross the bus\n",
-               (unsigned long long)mode.capacity, (unsigned long long)slots, (double)slots * 32.0 / 1073741824.0);
-    } else if (c.dp < 0 && 2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) > 67108864.0) printf("WARNING: the expected DP count exceeds 2^26 host entries even at -dp 32\n");
+    if (c.kdpdev) mode.dpt.banner(pl.cap);
+    else if (c.dp < 0 && 2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) > 67108864.0) printf("WARNING: the expected DP count exceeds 2^26 host entries even at -dp 32\n");
     if (c.sym) printf("Kangaroo: symmetric walk (negation map), %u jump points, jump scale %g\n", p.wh.jumps, p.wh.jumpscale);
     Shared sh(p);
     mode.prepare(p, sh);

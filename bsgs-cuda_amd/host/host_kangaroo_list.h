@@ -5,9 +5,11 @@
 // closing lines.  A walk supplies the rest (host_kangaroo_multi.cpp ListMode: the plain walk, Q_k counted from -pk, the key in the flags;
 // host_kangaroo_symlist.cpp SymListMode: the symmetric walk, Q_k counted from the middle of the range, the key beside the flags): its table, where offsets
 // count from, how an offset is drawn, the device's herd, where a state keeps its key, what a record does to the table.
+// -kdpkeys: the table in device memory is DevDpTable's (host_kangaroo_dptable.h), the member dpt; the list says which owner words are legal, sizes the table
+// by sqrt(L_open W), and hands what DevDpTable::take names a pair or a record alone to the walk's table.
 #pragma once
+#include "host_kangaroo_dptable.h"
 #include "host_kangaroo_multi.h"
-#include "host_kangaroo_run.h"
 
 #include <map>
 
@@ -17,7 +19,7 @@ template <class Table> struct ListSearch : Mode {
     ListSearch(const KangConfig &c, const std::vector<Affine> &P) : c(c), P(P), L((uint32_t)P.size())
     {
         if (c.cpuseed) herd_label = "herds (host), engine ";
-        if (c.kdpkeys) { counts_records = false; bound_launch = true; dp_free = c.dp < 0; }      // -kdpkeys: the launch counts, and is kept within the record buffer
+        dpt.enable(c, *this);
     }
     // ---- what a walk supplies
     virtual void own_settings(Prologue &) {}                                       // its header fields, and its part of "made with other settings"
@@ -35,17 +37,7 @@ template <class Table> struct ListSearch : Mode {
     virtual void closing() const {}                                                // its line between the job's figures and the engines'
 
     std::string fingerprint(const Prologue &p, const WorkHeader &h) const override { return keys_fingerprint(P, p.lo, p.hi, h); }
-    // a key is known: its KEY[n] block on the console and in win.txt at once, through key_lines as the BSGS path writes it
-    void report(uint32_t k)
-    {
-        std::string console;
-        const std::string win = key_lines((int)k + 1, table->key(k), P[k], console);
-        fputs(console.c_str(), stdout);
-        fflush(stdout);
-        std::ofstream f(c.dir + "/win.txt", std::ios::app | std::ios::binary);
-        f << win;
-        found_n++;
-    }
+    void report(uint32_t k) { report_key(c.dir, (int)k + 1, table->key(k), P[k]); found_n++; }      // a key is known
     bool before_devices(Prologue &p) override
     {
         pro = &p;
@@ -67,19 +59,10 @@ template <class Table> struct ListSearch : Mode {
             hs::affine_to_le(Q[k], &qxy[64 * (size_t)k], &qxy[64 * (size_t)k + 32]);
         }
         const uint64_t file_entries = p.resume ? p.wf.h.table : 0;
-        if (c.kdpkeys && p.resume) {                                               // the file's entries go to the device once they are verified (resumed()); tag 0 stays here
-            std::vector<uint8_t> own;
-            for (uint64_t i = 0; i < p.wf.h.table; i++) {
-                const uint8_t *en = &p.wf.table[32 * i];
-                uint64_t k64; uint32_t owner;
-                memcpy(&k64, en, 8); memcpy(&owner, en + 28, 4);
-                if (!table->owner_fits(owner)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
-                std::vector<uint8_t> &to = k64 ? pending : own;
-                to.insert(to.end(), en, en + 32);
-            }
-            p.wf.table.swap(own);
+        if (c.kdpkeys && p.resume) {                                               // an entry's owner word is 0 or names a key of this list
+            const Table *t = table.get();
+            if (!dpt.split(p.wf.table, [t](uint32_t owner) { return t->owner_fits(owner); })) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
             p.wf.h.table = p.wf.table.size() / 32;
-            dev_entries = pending.size() / 32;
         }
         if (p.resume) {                                                            // the file's solved keys are in win.txt already: counted, not written again
             const uint32_t before = table->solved();
@@ -89,12 +72,8 @@ template <class Table> struct ListSearch : Mode {
         }
         open0 = L - table->solved();
         if (!open0) printf("Found %d of %u\n", found_n, L);
-        if (c.kdpkeys && open0) {                                                  // the table in device memory: -kdpdev's rule with sqrt(L_open W) in the place of sqrt(W)
-            const double sq = std::sqrt((double)open0 * (double)p.W);
-            capacity = dpdev_capacity(sq, c.kdpn);
-            while (p.resume && capacity < 2 * file_entries && capacity < (1ull << 31)) capacity *= 2;      // (a file that holds more than this run would plan for)
-            dp_fixed = c.dp >= 0 ? c.dp : (int)dpdev_dp(sq, capacity);
-        }
+        // the table in device memory: -kdpdev's rule with sqrt(L_open W) in the place of sqrt(W)
+        if (c.kdpkeys && open0) dp_fixed = dpt.plan(c, std::sqrt((double)open0 * (double)p.W), file_entries);
         return open0 != 0;
     }
     // after the prologue: the expectation, the assignment of wild kangaroos to keys (-wl: as the saved states name it), the offsets of the initial herds in
@@ -189,74 +168,32 @@ template <class Table> struct ListSearch : Mode {
         }
         return nullptr;
     }
-    // -kdpkeys: the keyed table after the key list (a walk's setup() ends with it)
-    const char *begin_table(bsgs_dev *dev) const
-    {
-        return !c.kdpkeys || bsgs_kangaroo_dptable_begin_keys(dev, capacity) == BSGS_OK ? nullptr : "bsgs_kangaroo_dptable_begin_keys";
-    }
-    // -kdpkeys: the walk, the insert and the pairing in device memory; only the hand-backs reach the collector, and the DP count is the walk's
+    // -kdpkeys: the keyed table after the key list (a walk's setup() ends with dpt.begin); the launch, the load at -wl and the read for a save are its own
     int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &s) override
     {
-        if (!c.kdpkeys) return Mode::launch(dev, e, steps, recs, cap, n, dropped, s);
-        uint64_t seen = 0, entries = 0;
-        const int rc = bsgs_kangaroo_run_dptable_keys(dev, steps, recs, cap, n, &seen, &entries, dropped, nullptr);
-        if (rc != BSGS_OK) return rc;
-        uint64_t dead = 0;
-        for (uint32_t i = 0; i < *n; i++) dead += recs[i].reserved != BSGS_KANGAROO_DPT_STORED && (recs[i].flags & BSGS_KANGAROO_DEAD);
-        s.dps += seen - std::min(seen, dead);
-        dev_entries = entries;
-        return rc;
+        return dpt.on ? dpt.launch(dev, steps, recs, cap, n, dropped, s) : Mode::launch(dev, e, steps, recs, cap, n, dropped, s);
     }
-    // -kdpkeys -wl: the file's entries, verified, into the device table; a tag that occurs twice, is 0 or finds no slot: the section does not load
-    std::string resumed(bsgs_dev *dev, uint32_t e, Shared &s) override
-    {
-        (void)e; (void)s;
-        if (!c.kdpkeys || pending.empty()) return "";
-        uint64_t stored_n = 0, dup = 0, zero = 0, full = 0, entries = 0;
-        const auto ts = Clock::now();
-        if (bsgs_kangaroo_dptable_load(dev, (const bsgs_kangaroo_dp_entry *)pending.data(), pending.size() / 32, &stored_n, &dup, &zero, &full, &entries) != BSGS_OK)
-            return std::string("bsgs_kangaroo_dptable_load: ") + bsgs_last_error();
-        if (dup || full || zero) return "-kangaroo -wl: the table section of " + pro->wl_path + " does not load";
-        printf("[startup] %-44s %.3fs\n", ("table (GPU memory), " + std::to_string(entries) + " entries").c_str(), since(ts));
-        dev_entries = entries;
-        std::vector<uint8_t>().swap(pending);
-        return "";
-    }
-    // -kdpkeys: the device table as it stands, for save()
-    std::string fetch(bsgs_dev *dev, uint32_t e, Shared &s) override
-    {
-        (void)e; (void)s;
-        if (!c.kdpkeys) return "";
-        uint64_t n = 0;
-        if (bsgs_kangaroo_dptable_read(dev, nullptr, 0, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();      // the count alone
-        std::vector<uint8_t> got(32 * n);
-        if (n && bsgs_kangaroo_dptable_read(dev, (bsgs_kangaroo_dp_entry *)got.data(), n, &n) != BSGS_OK) return std::string("bsgs_kangaroo_dptable_read: ") + bsgs_last_error();
-        if (32 * n != got.size()) return "bsgs_kangaroo_dptable_read: the table changed between the count and the read";
-        std::lock_guard<std::mutex> lk(dev_m);
-        dev_table.swap(got);
-        return "";
-    }
-    size_t table_size() const { return table->size() + (size_t)dev_entries.load(); }      // "in the table": the host's entries and the device's
+    std::string resumed(bsgs_dev *dev, uint32_t, Shared &) override { return dpt.resumed(dev, pro->wl_path); }
+    std::string fetch(bsgs_dev *dev, uint32_t, Shared &) override { return dpt.fetch(dev); }
+    size_t table_size() const { return table->size() + (size_t)dpt.entries.load(); }      // "in the table": the host's entries and the device's
     bool record(uint32_t e, const bsgs_kangaroo_record &r, Shared &s) override
     {
         std::vector<Event> ev;
         const uint32_t kid = (uint32_t)(e * pro->pl.kn + r.kangaroo);
-        if (c.kdpkeys) {                                                           // a hand-back: `reserved` = reason | key << 8, or the stored half of a pair
-            if (r.reserved == BSGS_KANGAROO_DPT_STORED) { stored = r; have_stored = true; return true; }      // the entry the next record met
-            bsgs_kangaroo_record w = r;                                            // the record as the walk wrote it
-            w.reserved = r.reserved >> BSGS_KANGAROO_DPT_KEY_SHIFT;
-            if ((r.reserved & ((1u << BSGS_KANGAROO_DPT_KEY_SHIFT) - 1u)) == BSGS_KANGAROO_DPT_DUPLICATE) {
-                if (!have_stored) return true;                                     // (never: the device does not split a pair)
-                have_stored = false;
-                if (!table->owner_fits(stored.flags)) {                            // the table names a key the list does not have
-                    std::lock_guard<std::mutex> lk(s.err_m);
-                    if (s.err.empty()) s.err = "-kangaroo -kdpkeys: the table in GPU memory is damaged: an entry names owner " + std::to_string(stored.flags) + ", the list has " + std::to_string(L) + " keys";
-                    s.failed = true; s.stop = true;
-                    return false;
-                }
-                add_pair_record(stored, w, kid, ev);
-            } else add_record(w, kid, ev);                                         // DEAD, tag 0, a full device table -- the host's own map, as without the flag
-        } else add_record(r, kid, ev);
+        const DevDpTable::Taken t = dpt.take(r);                                   // t.walk: the record as the walk wrote it
+        switch (t.kind) {
+        case DevDpTable::STORED_HALF: case DevDpTable::ORPHAN: return true;
+        case DevDpTable::PAIR:
+            if (!table->owner_fits(t.stored->flags)) {                             // the table names a key the list does not have
+                std::lock_guard<std::mutex> lk(s.err_m);
+                if (s.err.empty()) s.err = "-kangaroo -kdpkeys: the table in GPU memory is damaged: an entry names owner " + std::to_string(t.stored->flags) + ", the list has " + std::to_string(L) + " keys";
+                s.failed = true; s.stop = true;
+                return false;
+            }
+            add_pair_record(*t.stored, t.walk, kid, ev);
+            break;
+        default: add_record(t.walk, kid, ev);                                      // no -kdpkeys, or what the device hands back alone: the host's own map
+        }
         for (const Event &x : ev) if (x.what == Table::RESEED) s.push_reseed(e, r.kangaroo);
         on_events(ev);
         return true;
@@ -276,12 +213,9 @@ template <class Table> struct ListSearch : Mode {
     }
     const WorkKeys *save(WorkHeader &h, std::vector<uint8_t> &entries) override
     {
-        std::lock_guard<std::mutex> lk(dev_m);
-        h.false_matches = table->false_matches(); h.reseeds = table->reseeds(); h.table = table->size() + dev_table.size() / 32;
+        h.false_matches = table->false_matches(); h.reseeds = table->reseeds();
         save_own(h);
-        entries.swap(dev_table);                                                   // -kdpkeys: what fetch() read when the herds were downloaded -- moved, not copied: every
-        std::vector<uint8_t>().swap(dev_table);                                    // save follows a fetch() of its own
-        entries.reserve(entries.size() + 32 * table->size());
+        dpt.save(h, entries, table->size());                                       // -kdpkeys: the device's entries first
         table->write_entries(entries);
         table->write_keys(wk);
         return &wk;
@@ -306,13 +240,7 @@ template <class Table> struct ListSearch : Mode {
     uint32_t open0 = 0, last_solved = 0;
     uint64_t half = 0, steps_mark = 0;
     double overhead = 0.0, exp_lo = 0.0, exp_hi = 0.0;
-    // -kdpkeys
-    uint64_t capacity = 0;                         // of the device table
-    std::atomic<uint64_t> dev_entries{0};          // entries in it after the last launch
-    std::vector<uint8_t> pending, dev_table;       // -wl: the file's entries on their way to the device; the device table as fetch() read it
-    std::mutex dev_m;
-    bsgs_kangaroo_record stored;                   // the first record of a handed-back pair, until its record comes
-    bool have_stored = false;
+    DevDpTable dpt;                                // -kdpkeys
 };
 
 // bsgs_mi355x -kangaroo -infile FILE with the walk of ModeT: every key of the list in [pk, pke] with ONE herd per engine
@@ -330,12 +258,7 @@ template <class ModeT> int list_main(const KangConfig &c)
     ModeT mode(c, P);
     p.complete(c, mode);                                                           // dp, kn, the jump mean and the launch length from W, as for one key
     if (!p.go) return 0;
-    if (c.kdpkeys) {
-        uint64_t slots = 128;
-        while (slots < 2 * (mode.capacity + p.pl.cap)) slots *= 2;
-        printf("Kangaroo: distinguished points stay in GPU memory (-kdpkeys): table of %llu entries, %llu slots, %.2f GiB; hand-backs only cross the bus\n",
-               (unsigned long long)mode.capacity, (unsigned long long)slots, (double)slots * 32.0 / 1073741824.0);
-    }
+    if (c.kdpkeys) mode.dpt.banner(p.pl.cap);
     Shared sh(p);
     mode.prepare(p, sh);
     const Outcome o = run(c, p, sh, mode);

@@ -150,33 +150,39 @@ bool MultiKeyTable::restore(const uint8_t *entries, uint64_t n, uint64_t false_m
     return true;
 }
 
-// one scripted record into the table, its event lines printed; false: the record does not parse.  stored (-selftest kangaroo-dpkeys): the fields of the
-// S, item in front of the record -- tag, d, kangaroo, owner -- and the record is judged against that entry as a pair
-static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::string &rec, const std::vector<std::string> *stored = nullptr)
+// one scripted record into the table, its event lines printed; false: the record does not parse.  dpt (-selftest kangaroo-dpkeys): the record goes through
+// DevDpTable::take as the device would hand it back -- paired: as the duplicate behind the stored half taken before it, never a dead record -- and is judged
+// as take() names it
+static bool multi_scripted_record(MultiKeyTable &tab, size_t n_keys, const std::string &rec, kang::DevDpTable *dpt = nullptr, bool paired = false)
 {
     const std::vector<std::string> f = kang::split_commas(rec);
-    if (f.size() != 4 || f[0].empty() || !strchr("TWD", f[0][0]) || (f[0][0] != 'W' && f[0].size() != 1)) return false;
-    uint32_t flags = f[0][0] == 'D' ? BSGS_KANGAROO_DEAD : 0u;
+    if (f.size() != 4 || f[0].empty() || !strchr(paired ? "TW" : "TWD", f[0][0]) || (f[0][0] != 'W' && f[0].size() != 1)) return false;
+    bsgs_kangaroo_record r;
+    memset(&r, 0, sizeof r);
+    r.flags = f[0][0] == 'D' ? BSGS_KANGAROO_DEAD : 0u;
+    unsigned long k = 0;
     if (f[0][0] == 'W') {
         if (f[0].size() < 2) return false;
-        const unsigned long k = strtoul(f[0].c_str() + 1, nullptr, 10);
+        k = strtoul(f[0].c_str() + 1, nullptr, 10);
         if (k >= n_keys) return false;
-        flags = BSGS_KANGAROO_WILD | (uint32_t)k << BSGS_KANGAROO_KEY_SHIFT;
+        r.flags = BSGS_KANGAROO_WILD | (uint32_t)k << BSGS_KANGAROO_KEY_SHIFT;
     }
     Scalar x, dd;
     if (!hs::fe_from_hex(x, f[1]) || !hs::fe_from_hex(dd, f[2]) || dd.l[2] || dd.l[3]) return false;
-    uint8_t xb[32];
-    hs::fe_to_le(x, xb);
+    hs::fe_to_le(x, r.x);
+    memcpy(r.d, &dd.l[0], 16);
+    r.kangaroo = (uint32_t)strtoul(f[3].c_str(), nullptr, 10);
+    kang::DevDpTable off;
+    const kang::DevDpTable::Taken t = (dpt ? dpt : &off)->take_scripted(r, (uint32_t)k, paired);
+    const u128 d = ((u128)dd.l[1] << 64) | dd.l[0];
     std::vector<MultiKeyTable::Event> ev;
-    if (stored) {
-        Scalar tag, ed;
-        if (stored->size() != 5 || f[0][0] == 'D' || !hs::fe_from_hex(tag, (*stored)[1]) || tag.l[1] || tag.l[2] || tag.l[3] || !hs::fe_from_hex(ed, (*stored)[2]) || ed.l[2] || ed.l[3]) return false;
-        if (x.l[0] != tag.l[0]) { fprintf(stderr, "the record does not share the tag of the stored entry it is paired with\n"); return false; }
-        const uint32_t owner = (uint32_t)strtoul((*stored)[4].c_str(), nullptr, 10);
-        if (!tab.owner_fits(owner)) { fprintf(stderr, "the table is damaged: an entry names owner %u, the list has %zu keys\n", owner, n_keys); return false; }
-        tab.add_pair((i128)(((u128)ed.l[1] << 64) | ed.l[0]), (uint32_t)strtoul((*stored)[3].c_str(), nullptr, 10), owner, ((u128)dd.l[1] << 64) | dd.l[0],
-                     (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, ev);
-    } else tab.add(xb, ((u128)dd.l[1] << 64) | dd.l[0], (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, ev);
+    if (t.kind == kang::DevDpTable::PAIR) {
+        if (!tab.owner_fits(t.stored->flags)) { fprintf(stderr, "the table is damaged: an entry names owner %u, the list has %zu keys\n", t.stored->flags, n_keys); return false; }
+        i128 ed;
+        memcpy(&ed, t.stored->d, 16);
+        tab.add_pair(ed, t.stored->kangaroo, t.stored->flags, d, r.kangaroo, r.flags, ev);
+    } else if (t.kind == kang::DevDpTable::ALONE || t.kind == kang::DevDpTable::NOT_MINE) tab.add(r.x, d, r.kangaroo, r.flags, ev);
+    else return false;
     for (const MultiKeyTable::Event &e : ev) switch (e.what) {
         case MultiKeyTable::NEW: printf("new\n"); break;
         case MultiKeyTable::REPEAT: printf("repeat\n"); break;
@@ -204,7 +210,11 @@ static void print_summary(const MultiKeyTable &tab)
 // (W<k>: a wild kangaroo of the key at list position k, from 0; D: a dead record).  A key equal to pk*G is solved up front: "presolved <k>".  One line per
 // event of a record: "new", "repeat", "reseed <kangaroo>", "false", "link <j> <k>", "found <k> <key hex>"; then
 // "summary <stored> <false matches> <reseeds> <links kept> <links resolved> <keys solved>".
-int kangaroo_multi_selftest(const std::vector<std::string> &a)
+// -selftest kangaroo-dpkeys [sym] <pk hex> <pke hex> <pubkey>[,<pubkey>...] <item>...: the hand-back rule of -kdpkeys without a GPU, every item through
+// DevDpTable::take.  An item is a scripted record as -selftest kangaroo-multi (sym: kangaroo-symlist) takes it -- what the device hands back alone: DEAD, tag
+// 0, a full table -- and goes through the host's own map; or S,<tag hex>,<d hex>,<kangaroo>,<owner> followed by its record: a duplicate, judged against the
+// stored entry it came with.  The same event and summary lines.
+static int multi_selftest(const std::vector<std::string> &a, bool dpkeys)
 {
     if (a.size() < 3) return 2;
     Scalar lo, hi; u128 W;
@@ -212,51 +222,33 @@ int kangaroo_multi_selftest(const std::vector<std::string> &a)
     if (!kang::parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
     MultiKeyTable tab(lo, W, pubs);
     presolve_scripted(tab, pubs, lo);
-    for (size_t i = 3; i < a.size(); i++) if (!multi_scripted_record(tab, pubs.size(), a[i])) return 2;
+    kang::DevDpTable dpt;
+    dpt.on = dpt.keyed = dpkeys;
+    if (!dpt.scripted_items(a, [&](const std::string &rec, bool paired) { return multi_scripted_record(tab, pubs.size(), rec, &dpt, paired); })) return 2;
     print_summary(tab);
     return 0;
 }
-
-// -selftest kangaroo-dpkeys [sym] <pk hex> <pke hex> <pubkey>[,<pubkey>...] <item>...: the hand-back rule of -kdpkeys without a GPU.  An item is a scripted
-// record as -selftest kangaroo-multi (sym: kangaroo-symlist) takes it -- what the device hands back alone: DEAD, tag 0, a full table -- and goes through the
-// host's own map; or S,<tag hex>,<d hex>,<kangaroo>,<owner> followed by its record: a duplicate, judged against the stored entry it came with.  The same event
-// and summary lines.
-int kangaroo_dpkeys_selftest(const std::vector<std::string> &args)
+int kangaroo_multi_selftest(const std::vector<std::string> &a) { return multi_selftest(a, false); }
+int kangaroo_dpkeys_selftest(const std::vector<std::string> &a)
 {
-    if (!args.empty() && args[0] == "sym") return kangaroo_dpkeys_sym_selftest(std::vector<std::string>(args.begin() + 1, args.end()));
-    const std::vector<std::string> &a = args;
-    if (a.size() < 3) return 2;
-    Scalar lo, hi; u128 W;
-    std::vector<Affine> pubs;
-    if (!kang::parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
-    MultiKeyTable tab(lo, W, pubs);
-    presolve_scripted(tab, pubs, lo);
-    for (size_t i = 3; i < a.size(); i++) {
-        if (a[i].compare(0, 2, "S,") != 0) { if (!multi_scripted_record(tab, pubs.size(), a[i])) return 2; continue; }
-        if (i + 1 >= a.size()) return 2;                              // a stored entry without its record
-        const std::vector<std::string> s = kang::split_commas(a[i]);
-        if (!multi_scripted_record(tab, pubs.size(), a[++i], &s)) return 2;
-    }
-    print_summary(tab);
-    return 0;
+    return !a.empty() && a[0] == "sym" ? kangaroo_dpkeys_sym_selftest(std::vector<std::string>(a.begin() + 1, a.end())) : multi_selftest(a, true);
 }
 
 // -selftest kangaroo-dpkeys-plan <pk hex> <pke hex> <CUs> <min launch> <dp or -1> <kn or 0> <kdpn or 0> <L>: the plan of -kdpkeys for one engine and L open
-// keys without a GPU -- -kdpdev's with sqrt(L W) in the place of sqrt(W) for the capacity and dp -- as -selftest kangaroo-dpdev-plan prints it
+// keys without a GPU -- -kdpdev's with sqrt(L W) in the place of sqrt(W) for the capacity and dp, through DevDpTable::plan --, one line:
+// "plan <dp> <kn> <per thread> <S> <record buffer> <capacity>"
 int kangaroo_dpkeys_plan_selftest(const std::vector<std::string> &a)
 {
     if (a.size() != 8) return 2;
     kang::KangConfig c;
-    c.pk = a[0]; c.pke = a[1];
+    c.pk = a[0]; c.pke = a[1]; c.dp = atoi(a[4].c_str()); c.kdpn = strtoull(a[6].c_str(), nullptr, 0);
     kang::Prologue p(c);
-    const int cus = atoi(a[2].c_str()), dp_arg = atoi(a[4].c_str());
     const uint64_t L = strtoull(a[7].c_str(), nullptr, 0);
     if (!L || L > BSGS_KANGAROO_MAX_KEYS) return 2;
-    const double sq = std::sqrt((double)L * (double)p.W);
-    const uint64_t capacity = kang::dpdev_capacity(sq, strtoull(a[6].c_str(), nullptr, 0));
-    kang::Plan pl = kang::plan_herd(p.sqrtW, 1, cus, dp_arg >= 0 ? dp_arg : (int)kang::dpdev_dp(sq, capacity), strtoull(a[5].c_str(), nullptr, 0));
-    kang::plan_launch(pl, p.sqrtW, 0.0, atof(a[3].c_str()), true, dp_arg < 0);
-    printf("plan %u %llu %u %u %u %llu\n", pl.dp, (unsigned long long)pl.kn, pl.G, pl.S, pl.cap, (unsigned long long)capacity);
+    kang::DevDpTable dpt;
+    kang::Plan pl = kang::plan_herd(p.sqrtW, 1, atoi(a[2].c_str()), dpt.plan(c, std::sqrt((double)L * (double)p.W), 0), strtoull(a[5].c_str(), nullptr, 0));
+    kang::plan_launch(pl, p.sqrtW, 0.0, atof(a[3].c_str()), true, c.dp < 0);
+    printf("plan %u %llu %u %u %u %llu\n", pl.dp, (unsigned long long)pl.kn, pl.G, pl.S, pl.cap, (unsigned long long)dpt.capacity);
     return 0;
 }
 
@@ -327,7 +319,7 @@ struct ListMode : ListSearch<MultiKeyTable> {
         const Plan &pl = pro->pl;
         if (bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup";
         if (bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) return "bsgs_kangaroo_set_keys";
-        return begin_table(dev);
+        return dpt.begin(dev);
     }
     void add_record(const bsgs_kangaroo_record &r, uint32_t kid, std::vector<MultiKeyTable::Event> &ev) override
     {

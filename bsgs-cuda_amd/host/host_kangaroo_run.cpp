@@ -32,6 +32,16 @@ std::vector<size_t> kang::comb_states(const Comb &C, const std::vector<i128> &d,
     return inf;
 }
 
+void kang::report_key(const std::string &dir, int listpos, const Scalar &key, const Affine &pub)
+{
+    std::string console;
+    const std::string win = key_lines(listpos, key, pub, console);
+    fputs(console.c_str(), stdout);
+    fflush(stdout);
+    std::ofstream f(dir + "/win.txt", std::ios::app | std::ios::binary);
+    f << win;
+}
+
 void kang::plan_launch(Plan &pl, double sqrtW, double expected0, double min_launch, bool bound, bool dp_free)
 {
     const double Nk = (double)pl.kn * pl.engines, half = 2097152.0;

@@ -1,7 +1,9 @@
-// host_kangaroo_run.h -- the one prologue and the one run loop of bsgs_mi355x -kangaroo (host_kangaroo_run.cpp), and the seam the two modes
-// stand behind: KeyMode (host_kangaroo.cpp: one public key, plain and -ksym) and ListMode (host_kangaroo_multi.cpp: -infile).  The driver owns the engine
-// threads, the collector, the monitor with the save handshake, the signals, the shutdown and the work file's common part; a Mode owns its table of
-// distinguished points, how a kangaroo is started and what a record means.
+// host_kangaroo_run.h -- the one prologue and the one run loop of bsgs_mi355x -kangaroo (host_kangaroo_run.cpp), and the seam the modes stand
+// behind: KeyMode (host_kangaroo.cpp: one public key, plain and -ksym), ListSearch<Table> (host_kangaroo_list.h: -infile) with its two walks ListMode
+// (host_kangaroo_multi.cpp) and SymListMode (host_kangaroo_symlist.cpp: -kwalk sym), GenMode and SearchMode (host_kangaroo_tames.cpp: -ktamesgen, -ktames).
+// The driver owns the engine threads, the collector, the monitor with the save handshake, the signals, the shutdown and the work file's common part; a Mode
+// owns its table of distinguished points, how a kangaroo is started and what a record means.  A table kept in device memory (-kdpdev, -kdpkeys) is reached
+// through DevDpTable (host_kangaroo_dptable.h), which KeyMode and ListSearch hold behind the launch, resumed and fetch hooks.
 #pragma once
 #include "host_kangaroo.h"
 
@@ -122,6 +124,10 @@ public:
 // kangaroo's share of it within [min_launch, 1024], and the record buffer for twice the records a launch is expected to write (at most 2^22).  bound: S, then
 // dp (only when dp_free), give way until kn S / 2^dp is at most 2^21, half of the largest record buffer
 void plan_launch(Plan &pl, double sqrtW, double expected0, double min_launch, bool bound, bool dp_free);
+
+// a key of a list is known: its KEY[n] block (n = listpos, from 1) on the console and at the end of <dir>/win.txt at once, through key_lines as the BSGS path
+// writes it
+void report_key(const std::string &dir, int listpos, const Scalar &key, const Affine &pub);
 
 enum Outcome { DONE, GAVE_UP, BUDGET, INTERRUPTED, ENDED };           // ENDED: stopped for none of the other reasons
 // engines, collector, monitor, shutdown and the last save; the mode turns the outcome into its closing text and exit code

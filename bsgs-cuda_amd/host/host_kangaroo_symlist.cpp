@@ -222,35 +222,40 @@ private:
     uint32_t solved_ = 0;
 };
 
-// one scripted record into the table, its event lines printed; false: the record does not parse.  stored (-selftest kangaroo-dpkeys sym): the fields of the
-// S, item in front of the record -- tag, d, kangaroo, owner word -- and the record is judged against that entry as a pair
-bool scripted_record(SymListTable &tab, size_t n_keys, const std::string &rec, const std::vector<std::string> *stored = nullptr)
+// one scripted record into the table, its event lines printed; false: the record does not parse.  dpt (-selftest kangaroo-dpkeys sym): the record goes through
+// DevDpTable::take as the device would hand it back -- paired: as the duplicate behind the stored half taken before it, never a dead record -- and is judged
+// as take() names it
+bool scripted_record(SymListTable &tab, size_t n_keys, const std::string &rec, DevDpTable *dpt = nullptr, bool paired = false)
 {
     const std::vector<std::string> f = split_commas(rec);
-    if (f.size() != 4 || f[0].empty() || !strchr("TWNDC", f[0][0])) return false;
+    if (f.size() != 4 || f[0].empty() || !strchr(paired ? "TWN" : "TWNDC", f[0][0])) return false;
     const char t = f[0][0];
-    uint32_t flags = t == 'D' ? BSGS_KANGAROO_DEAD : t == 'C' ? BSGS_KANGAROO_DEAD | BSGS_KANGAROO_CYCLE : 0u, key = 0;
+    bsgs_kangaroo_record r;
+    memset(&r, 0, sizeof r);
+    r.flags = t == 'D' ? BSGS_KANGAROO_DEAD : t == 'C' ? BSGS_KANGAROO_DEAD | BSGS_KANGAROO_CYCLE : 0u;
     if (t == 'W' || t == 'N') {
         if (f[0].size() < 2) return false;
         const unsigned long k = strtoul(f[0].c_str() + 1, nullptr, 10);
         if (k >= n_keys) return false;
-        key = (uint32_t)k;
-        flags = BSGS_KANGAROO_WILD | (t == 'N' ? BSGS_KANGAROO_NEG : 0u);
+        r.reserved = (uint32_t)k;                                     // the key beside the flags
+        r.flags = BSGS_KANGAROO_WILD | (t == 'N' ? BSGS_KANGAROO_NEG : 0u);
     } else if (f[0].size() != 1) return false;
     Scalar x, dd;
     if (!hs::fe_from_hex(x, f[1]) || !hs::fe_from_hex(dd, f[2]) || dd.l[2] || dd.l[3]) return false;
-    uint8_t xb[32];
-    hs::fe_to_le(x, xb);
+    hs::fe_to_le(x, r.x);
+    memcpy(r.d, &dd.l[0], 16);
+    r.kangaroo = (uint32_t)strtoul(f[3].c_str(), nullptr, 10);
+    DevDpTable off;
+    const DevDpTable::Taken tk = (dpt ? dpt : &off)->take_scripted(r, r.reserved, paired);
+    const u128 d = ((u128)dd.l[1] << 64) | dd.l[0];
     std::vector<SymListTable::Event> ev;
-    if (stored) {
-        Scalar tag, ed;
-        if (stored->size() != 5 || t == 'D' || t == 'C' || !hs::fe_from_hex(tag, (*stored)[1]) || tag.l[1] || tag.l[2] || tag.l[3] || !hs::fe_from_hex(ed, (*stored)[2]) || ed.l[2] || ed.l[3]) return false;
-        if (x.l[0] != tag.l[0]) { fprintf(stderr, "the record does not share the tag of the stored entry it is paired with\n"); return false; }
-        const uint32_t owner = (uint32_t)strtoul((*stored)[4].c_str(), nullptr, 10);
-        if (!tab.owner_fits(owner)) { fprintf(stderr, "the table is damaged: an entry names owner %u, the list has %zu keys\n", owner, n_keys); return false; }
-        tab.add_pair((i128)(((u128)ed.l[1] << 64) | ed.l[0]), (uint32_t)strtoul((*stored)[3].c_str(), nullptr, 10), owner, ((u128)dd.l[1] << 64) | dd.l[0],
-                     (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, key, ev);
-    } else tab.add(xb, ((u128)dd.l[1] << 64) | dd.l[0], (uint32_t)strtoul(f[3].c_str(), nullptr, 10), flags, key, ev);
+    if (tk.kind == DevDpTable::PAIR) {
+        if (!tab.owner_fits(tk.stored->flags)) { fprintf(stderr, "the table is damaged: an entry names owner %u, the list has %zu keys\n", tk.stored->flags, n_keys); return false; }
+        i128 ed;
+        memcpy(&ed, tk.stored->d, 16);
+        tab.add_pair(ed, tk.stored->kangaroo, tk.stored->flags, d, r.kangaroo, r.flags, tk.walk.reserved, ev);
+    } else if (tk.kind == DevDpTable::ALONE || tk.kind == DevDpTable::NOT_MINE) tab.add(r.x, d, r.kangaroo, r.flags, tk.walk.reserved, ev);
+    else return false;
     for (const SymListTable::Event &e : ev) switch (e.what) {
         case SymListTable::NEW: printf("new\n"); break;
         case SymListTable::REPEAT: printf("repeat\n"); break;
@@ -279,22 +284,9 @@ void print_summary(const SymListTable &tab)
 // (W<k>: a wild kangaroo of the key at list position k, from 0; N<k>: one with NEG; D: a dead record; C: a cycle's dead record).  A key equal to
 // (pk + W/2)*G is solved up front: "presolved <k>".  One line per event of a record, as -selftest kangaroo-multi; then
 // "summary <stored> <false matches> <reseeds> <links kept> <links resolved> <keys solved> <cycles>".
-int kangaroo_symlist_selftest(const std::vector<std::string> &a)
-{
-    if (a.size() < 3) return 2;
-    Scalar lo, hi; u128 W;
-    std::vector<Affine> pubs;
-    if (!parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
-    SymListTable tab(lo, W, pubs);
-    presolve_scripted(tab, pubs);
-    for (size_t i = 3; i < a.size(); i++) if (!scripted_record(tab, pubs.size(), a[i])) return 2;
-    print_summary(tab);
-    return 0;
-}
-
 // -selftest kangaroo-dpkeys sym ...: the symmetric walk's part of -selftest kangaroo-dpkeys (host_kangaroo_multi.cpp describes the items); an owner word is
 // decimal, bit 31 for NEG
-int kangaroo_dpkeys_sym_selftest(const std::vector<std::string> &a)
+static int symlist_selftest(const std::vector<std::string> &a, bool dpkeys)
 {
     if (a.size() < 3) return 2;
     Scalar lo, hi; u128 W;
@@ -302,15 +294,14 @@ int kangaroo_dpkeys_sym_selftest(const std::vector<std::string> &a)
     if (!parse_range_pubs(a[0], a[1], a[2], lo, hi, W, pubs) || pubs.empty() || pubs.size() > BSGS_KANGAROO_MAX_KEYS) return 2;
     SymListTable tab(lo, W, pubs);
     presolve_scripted(tab, pubs);
-    for (size_t i = 3; i < a.size(); i++) {
-        if (a[i].compare(0, 2, "S,") != 0) { if (!scripted_record(tab, pubs.size(), a[i])) return 2; continue; }
-        if (i + 1 >= a.size()) return 2;                              // a stored entry without its record
-        const std::vector<std::string> s = split_commas(a[i]);
-        if (!scripted_record(tab, pubs.size(), a[++i], &s)) return 2;
-    }
+    DevDpTable dpt;
+    dpt.on = dpt.keyed = dpkeys;
+    if (!dpt.scripted_items(a, [&](const std::string &rec, bool paired) { return scripted_record(tab, pubs.size(), rec, &dpt, paired); })) return 2;
     print_summary(tab);
     return 0;
 }
+int kangaroo_symlist_selftest(const std::vector<std::string> &a) { return symlist_selftest(a, false); }
+int kangaroo_dpkeys_sym_selftest(const std::vector<std::string> &a) { return symlist_selftest(a, true); }
 
 // -selftest kangaroo-symlist-roundtrip <pk hex> <pke hex> <pubkeys> <split> <record>...: the first <split> records into a table, the table into a version-4
 // work file without herds (a temporary file; BSGS_SELFTEST_WORK names a path to write and keep instead; 1024 jump points, jump scale 1), the file into a fresh
@@ -387,7 +378,7 @@ struct SymListMode : ListSearch<SymListTable> {
         const Plan &pl = pro->pl;
         if (bsgs_kangaroo_setup_sym_keys(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap) != BSGS_OK) return "bsgs_kangaroo_setup_sym_keys";
         if (bsgs_kangaroo_set_keys(dev, qxy.data(), L) != BSGS_OK) return "bsgs_kangaroo_set_keys";
-        return begin_table(dev);
+        return dpt.begin(dev);
     }
     void add_record(const bsgs_kangaroo_record &r, uint32_t kid, std::vector<SymListTable::Event> &ev) override
     {

@@ -252,6 +252,24 @@ private:
     std::map<uint64_t, i128> held_;
 };
 
+// T entries (tag x, offset d) of a tame table against d*G on an open device that has a herd (bsgs_kangaroo_verify_points, tame flags), 2^20 at a time:
+// *bad = the first entry that does not match its offset, T when every one does.  The code of the call that failed, else BSGS_OK
+int verify_tame_entries(bsgs_dev *dev, const uint64_t *x, const i128 *d, uint64_t T, uint64_t *bad)
+{
+    uint8_t g[64];
+    hs::affine_to_le(hs::G, g, g + 32);
+    const uint64_t step = 1u << 20;
+    std::vector<uint32_t> fl((size_t)std::min(T, step), 0u);
+    *bad = T;
+    for (uint64_t pos = 0; pos < T; pos += step) {
+        uint32_t n_bad = 0, first = 0;
+        const int rc = bsgs_kangaroo_verify_points(dev, g, (uint32_t)std::min(T - pos, step), (const uint8_t *)&d[pos], fl.data(), &x[pos], &n_bad, &first, 1);
+        if (rc != BSGS_OK) return rc;
+        if (n_bad) { *bad = pos + first; break; }
+    }
+    return BSGS_OK;
+}
+
 // ---- -ktamesgen ---------------------------------------------------------------------------------------------------------------------------------------
 struct GenMode : Mode {
     GenMode(const KangConfig &c, const Prologue &p, TamesFile *from = nullptr) : c(c), T(c.ktn), Tplan(c.ktnplan ? c.ktnplan : c.ktn), from(from), rule(c.ktn)
@@ -358,17 +376,9 @@ struct GenMode : Mode {
         read_secs = since(tr);
         if (!c.verify) return "";
         const auto ts = Clock::now();
-        uint8_t g[64];
-        hs::affine_to_le(hs::G, g, g + 32);
-        const uint64_t step = 1u << 20;
-        std::vector<uint32_t> fl((size_t)std::min(T, step), 0u);
-        for (uint64_t pos = 0; pos < T; pos += step) {
-            const uint32_t m = (uint32_t)std::min(T - pos, step);
-            uint32_t n_bad = 0, first = 0;
-            if (bsgs_kangaroo_verify_points(dev, g, m, (const uint8_t *)&td[pos], fl.data(), &tx[pos], &n_bad, &first, 1) != BSGS_OK)
-                return std::string("bsgs_kangaroo_verify_points: ") + bsgs_last_error();
-            if (n_bad) { tx.clear(); td.clear(); return "Tame table is damaged: entry " + std::to_string(pos + first) + " does not match its offset"; }
-        }
+        uint64_t bad = 0;
+        if (verify_tame_entries(dev, tx.data(), td.data(), T, &bad) != BSGS_OK) return std::string("bsgs_kangaroo_verify_points: ") + bsgs_last_error();
+        if (bad < T) { tx.clear(); td.clear(); return "Tame table is damaged: entry " + std::to_string(bad) + " does not match its offset"; }
         printf("\n[verify] tame table: %llu entries %.3fs\n", (unsigned long long)T, since(ts));
         return "";
     }
@@ -521,16 +531,7 @@ struct SearchMode : Mode {
         herd_label = "herd (GPU, all wild), engine ";
     }
     std::string fingerprint(const Prologue &, const WorkHeader &) const override { return ""; }
-    void report(uint32_t k, const Scalar &key)
-    {
-        std::string console;
-        const std::string win = key_lines((int)k + 1, key, P[k], console);
-        fputs(console.c_str(), stdout);
-        fflush(stdout);
-        std::ofstream o(c.dir + "/win.txt", std::ios::app | std::ios::binary);
-        o << win;
-        found_n++;
-    }
+    void report(uint32_t k, const Scalar &key) { report_key(c.dir, (int)k + 1, key, P[k]); found_n++; }
     bool before_devices(Prologue &p) override
     {
         pro = &p;
@@ -693,7 +694,7 @@ struct SearchMode : Mode {
     double overhead = 0.0;
 };
 
-// every entry of the table against d*G on the first engine's device (bsgs_kangaroo_verify_points, tame flags), 2^20 at a time, before anything walks
+// every entry of the table against d*G on the first engine's device, before anything walks
 void tames_verify(const TamesFile &f, int gpu)
 {
     const auto ts = Clock::now();
@@ -702,17 +703,11 @@ void tames_verify(const TamesFile &f, int gpu)
     std::vector<uint8_t> jxy(64 * (size_t)BSGS_KANGAROO_JUMPS);
     for (uint32_t j = 0; j < BSGS_KANGAROO_JUMPS; j++) hs::affine_to_le(hs::G, &jxy[64 * (size_t)j], &jxy[64 * (size_t)j + 32]);
     CK(bsgs_kangaroo_setup(dev, jxy.data(), f.js.data(), f.dp, 64, 1, 64));      // the smallest herd: the verification's comb hangs on one
-    uint8_t g[64];
-    hs::affine_to_le(hs::G, g, g + 32);
-    const uint64_t T = f.x.size(), step = 1u << 20;
-    std::vector<uint32_t> fl((size_t)std::min(T, step), 0u);
-    for (uint64_t pos = 0; pos < T; pos += step) {
-        const uint32_t m = (uint32_t)std::min(T - pos, step);
-        uint32_t n_bad = 0, first = 0;
-        CK(bsgs_kangaroo_verify_points(dev, g, m, (const uint8_t *)&f.d[pos], fl.data(), &f.x[pos], &n_bad, &first, 1));
-        if (n_bad) { bsgs_dev_close(dev); die("Tame table is damaged: entry " + std::to_string(pos + first) + " does not match its offset"); }
-    }
+    const uint64_t T = f.x.size();
+    uint64_t bad = 0;
+    CK(verify_tame_entries(dev, f.x.data(), f.d.data(), T, &bad));
     bsgs_dev_close(dev);
+    if (bad < T) die("Tame table is damaged: entry " + std::to_string(bad) + " does not match its offset");
     printf("[verify] tame table: %llu entries %.3fs\n", (unsigned long long)T, since(ts));
 }
 
@@ -720,8 +715,7 @@ int tames_search(const KangConfig &c)
 {
     // the table is read before any device is looked for
     TamesFile f;
-    std::string path = c.ktames;
-    { struct stat sb; if (stat(path.c_str(), &sb) != 0 && stat((c.dir + "/" + path).c_str(), &sb) == 0) path = c.dir + "/" + path; }
+    const std::string path = find_tames(c, c.ktames);
     const std::string bad = read_tames(path, f, c.tames_sym ? TAMES_VERSION_SYM : TAMES_VERSION);
     if (!bad.empty()) die(std::string(c.tames_sym ? "-ktamessym: " : "-ktames: ") + bad);
     std::vector<std::string> pub_hex;
