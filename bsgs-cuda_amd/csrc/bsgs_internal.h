@@ -14,12 +14,14 @@ int bsgs_fail(int code, const char *fmt, ...);
     } while (0)
 #define fail bsgs_fail
 
+#define KANG_ROUTE_HEADER 256u                              // the outbox of a sharded distinguished-point table: 16 counts and 16 cursors (u64), then records
 #define KANG_REC_HEADER 64u                                 // a record buffer (the walk's rec, the match's tames_rec): u64 count of records, then records from byte 64
 
 // kangaroo.hip: the herd, its scratch, jump table and record buffer; kangaroo_seed.hip: the comb table, the staging of a seed call and the key list;
 // kangaroo_verify.hip: the one Q of a call and the list of failures; kangaroo_tames.hip: the tame table's image and the buffer of matched records;
 // kangaroo_tames_gen.hip: the table that grows during generation, whose handed-back records share the matched records' buffer; kangaroo_tames_extend.hip: its load and sorted read;
-// kangaroo_dptable.hip: the distinguished-point table of a search with its own buffer of hand-backs (both tables: KangTable); kangaroo_dptable_keys.hip: its insert for a key list
+// kangaroo_dptable.hip: the distinguished-point table of a search with its own buffer of hand-backs (both tables: KangTable); kangaroo_dptable_keys.hip: its insert for a key list;
+// kangaroo_dptable_shard.hip: its insert for one shard of a table divided over engines, with the outbox of the records that belong to other shards
 // the table in device memory (kangaroo_table.hip.h has the rule): tag[slots] (0 = empty), the offset of each, its owner (kangaroo, type; null for the tame
 // table), eight counters.  It exists where tag is set; slots is a power of two
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
@@ -56,6 +58,8 @@ struct bsgs_kangaroo {
     KangTable dpt;                         // bsgs_kangaroo_dptable_begin: the distinguished-point table of a search
     u32 *dpt_out = nullptr;                // its hand-backs of a launch: u64 places taken, u64 records handed back | 2 * cap records from byte 64
     bool dpt_keyed = false;                // bsgs_kangaroo_dptable_begin_keys: who[s].y is the work file's owner word (0 tame, 1 + key, bit 31 NEG), not a type
+    uint32_t dpt_shards = 0, dpt_shard = 0, dpt_base = 0;      // bsgs_kangaroo_dptable_begin_shard: shard dpt_shard of dpt_shards (0: the table is not divided), ids = dpt_base + local
+    u32 *dpt_route = nullptr;              // its outbox: u64 hist[16], u64 cursor[16] | cap records from byte KANG_ROUTE_HEADER, grouped by destination
 };
 
 struct bsgs_dev {
@@ -229,17 +233,24 @@ int bsgs_kang_table_loaded(bsgs_dev *d, const KangTable *t, hipError_t e, uint64
                            uint64_t *n_entries, const char *text);
 // behind a harvest (its caller has zeroed ctr[CTR_MET] before it): what it met against the entries counted (`what`: the table's name in the error)
 int bsgs_kang_table_met_check(uint64_t met, uint64_t entries, const char *what);
-// kangaroo_dptable.hip: the host side of the distinguished-point table, shared with kangaroo_dptable_keys.hip (the table for a key list).  `keyed`: the calls
-// of that unit; a table begun one way refuses the run and the insert of the other (BSGS_ERR_STATE), load, read and end serve both
-int bsgs_kang_dpt_begin(bsgs_dev *d, uint64_t capacity, bool keyed);
-int bsgs_kang_dpt_run(bsgs_dev *d, bool keyed, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen, uint64_t *n_entries,
-                      uint64_t *dropped, float *kernel_ms);
-int bsgs_kang_dpt_insert(bsgs_dev *d, bool keyed, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs, uint32_t *nrecs,
-                         uint64_t *n_entries, uint64_t *dropped);
+// kangaroo_dptable.hip: the host side of the distinguished-point table, shared with kangaroo_dptable_keys.hip (the table for a key list) and
+// kangaroo_dptable_shard.hip (the table divided over engines).  `kind`: whose calls; a table begun one way refuses the run and the insert of the others
+// (BSGS_ERR_STATE), load, read and end serve all.  `rt`: where the routed records of a sharded table go (null for the other kinds)
+enum { BSGS_DPT_EITHER = -1, BSGS_DPT_UNKEYED = 0, BSGS_DPT_KEYED = 1, BSGS_DPT_SHARDED = 2 };
+struct DptRouted { bsgs_kangaroo_record *recs; uint32_t max; uint32_t *n; uint32_t base; };      // n[dpt_shards]; base: added to the ids of this call's records
+int bsgs_kang_dpt_begin(bsgs_dev *d, uint64_t capacity, int kind);
+int bsgs_kang_dpt_run(bsgs_dev *d, int kind, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen, uint64_t *n_entries,
+                      uint64_t *dropped, float *kernel_ms, const DptRouted *rt = nullptr);
+int bsgs_kang_dpt_insert(bsgs_dev *d, int kind, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs, uint32_t *nrecs,
+                         uint64_t *n_entries, uint64_t *dropped, const DptRouted *rt = nullptr);
 int bsgs_kang_dpt_resolve(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blocks);      // the resolve kernel behind an insert, on the stream
 static inline uint32_t bsgs_kang_dpt_out_cap(const bsgs_kangaroo *k) { return 2u * k->cap; }      // every record of a launch a duplicate: two places each (cap <= 2^26)
 // kangaroo_dptable_keys.hip: the keyed insert of the records in k->rec (their count at its head) on the stream
 int bsgs_kang_dpt_insert_keys_launch(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blocks);
+// kangaroo_dptable_shard.hip: the sharded insert and the scatter of the foreign records in k->rec on the stream, ids = base + the record's; and, once the
+// stream has drained, the routed groups -> rt (cut at rt->max; *cut = records that did not fit)
+int bsgs_kang_dpt_insert_shard_launch(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blocks, uint32_t base);
+int bsgs_kang_dpt_routed_out(bsgs_dev *d, bsgs_kangaroo *k, uint64_t held, const DptRouted *rt, uint64_t *cut);
 // hand a finished "lines + overflow list" table to the engine (it becomes the owner of both buffers)
 int bsgs_install_lines(bsgs_dev *d, u32x4 *lines, int lplog, u64 *ovf, uint64_t ovf_n, uint64_t ht_items, uint64_t w,
                        uint64_t overflow_buckets);

@@ -368,7 +368,7 @@ void bsgs_kangaroo_release(bsgs_dev *d)
     if (!k) return;
     for (void *p : {(void *)k->st, (void *)k->chain, (void *)k->table, (void *)k->staging, (void *)k->flags, (void *)k->rec, (void *)k->idx, (void *)k->comb,
                     (void *)k->seed_in, (void *)k->seed_z, (void *)k->seed_out, (void *)k->mark, (void *)k->keys, (void *)k->verify_q, (void *)k->verify_out, (void *)k->tames,
-                    (void *)k->tames_rec, (void *)k->dpt_out})
+                    (void *)k->tames_rec, (void *)k->dpt_out, (void *)k->dpt_route})
         if (p) (void)hipFree(p);
     bsgs_kang_table_free(&k->gen);
     bsgs_kang_table_free(&k->dpt);

@@ -12,7 +12,8 @@
 //   load      32-byte entries of the caller's by the same rule, staged in chunks; the four outcomes are counted, nothing else comes back.
 //   harvest   strides over the slots and compacts the occupied ones into 32-byte entries, in any order.
 // The table for a key list (kangaroo_dptable_keys.hip) is this table with the work file's owner word where the type stands: its insert is that unit's kernel,
-// and resolve, load and harvest -- which copy who[s].y as it is -- and the host side below serve both.
+// and resolve, load and harvest -- which copy who[s].y as it is -- and the host side below serve both.  The table divided over engines
+// (kangaroo_dptable_shard.hip) is this table for one share of the tags with global kangaroo ids: its insert and scatter are that unit's kernels, the rest is here.
 #include "kangaroo_table.hip.h"
 
 #define DPT_LOAD_CHUNK BSGS_KANGAROO_DPT_LOAD_CHUNK
@@ -167,8 +168,10 @@ static void dpt_free(bsgs_kangaroo *k)
 {
     bsgs_kang_table_free(&k->dpt);
     if (k->dpt_out) (void)hipFree(k->dpt_out);
-    k->dpt_out = nullptr;
+    if (k->dpt_route) (void)hipFree(k->dpt_route);
+    k->dpt_out = k->dpt_route = nullptr;
     k->dpt_keyed = false;
+    k->dpt_shards = k->dpt_shard = k->dpt_base = 0;
 }
 
 static inline uint32_t dpt_out_cap(const bsgs_kangaroo *k) { return bsgs_kang_dpt_out_cap(k); }
@@ -188,12 +191,15 @@ int bsgs_kang_dpt_resolve(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blocks)
     return BSGS_OK;
 }
 
-// insert and resolve of the records in k->rec (their count at its head) on the stream; a keyed table takes the insert of kangaroo_dptable_keys.hip
-static int dpt_insert(bsgs_dev *d, bsgs_kangaroo *k)
+// insert and resolve of the records in k->rec (their count at its head) on the stream; a keyed table takes the insert of kangaroo_dptable_keys.hip, a
+// sharded one that of kangaroo_dptable_shard.hip (base: what it adds to the records' kangaroo ids)
+static int dpt_insert(bsgs_dev *d, bsgs_kangaroo *k, u32 base)
 {
     const u32 blocks = std::min((k->cap + 255u) / 256u, KT_INSERT_GRID_MAX);
     if (k->dpt_keyed) {
         if (int rc = bsgs_kang_dpt_insert_keys_launch(d, k, blocks)) return rc;
+    } else if (k->dpt_shards) {
+        if (int rc = bsgs_kang_dpt_insert_shard_launch(d, k, blocks, base)) return rc;
     } else {
         hipLaunchKernelGGL(kangaroo_dptable_insert_kernel, dim3(blocks), dim3(256), 0, d->stream, dpt_args(k));
         HIPCHK(hipGetLastError());
@@ -221,10 +227,21 @@ static int dpt_copy_out(bsgs_dev *d, bsgs_kangaroo *k, uint64_t places, bsgs_kan
 }
 
 // `table`: the call needs one; `want`: DPT_EITHER, or the kind of table the call is for.  A keyed table stands under a herd with a key list, that of
-// bsgs_kangaroo_setup_sym_keys included, which every other table call refuses.
-enum { DPT_EITHER = -1, DPT_UNKEYED = 0, DPT_KEYED = 1 };
+// bsgs_kangaroo_setup_sym_keys included, which every other table call refuses.  A sharded table stands under the unkeyed table's herds and holds global ids.
+enum { DPT_EITHER = BSGS_DPT_EITHER, DPT_UNKEYED = BSGS_DPT_UNKEYED, DPT_KEYED = BSGS_DPT_KEYED, DPT_SHARDED = BSGS_DPT_SHARDED };
 static int dpt_herd(bsgs_dev *d, bsgs_kangaroo **k, bool table, int want = DPT_UNKEYED)
 {
+    if (d && d->kangaroo && d->kangaroo->dpt.tag && d->kangaroo->dpt_shards && table && want != DPT_EITHER && want != DPT_SHARDED)
+        return fail(BSGS_ERR_STATE, "the table was begun by bsgs_kangaroo_dptable_begin_shard: bsgs_kangaroo_run_dptable_shard and bsgs_kangaroo_dptable_insert_shard fill it");
+    if (want == DPT_SHARDED) {
+        if (int rc = bsgs_kang_table_herd(d, k, &bsgs_kangaroo::dpt, "a distinguished-point table divided over engines serves the herds of bsgs_kangaroo_setup and bsgs_kangaroo_setup_sym",
+                                          table ? "bsgs_kangaroo_dptable_begin_shard first" : nullptr)) return rc;
+        if ((*k)->keys && (*k)->n_keys)
+            return fail(BSGS_ERR_STATE, "a distinguished-point table divided over engines serves one key: this herd has a key list (bsgs_kangaroo_set_keys)");
+        if (table && !(*k)->dpt_shards)
+            return fail(BSGS_ERR_STATE, "the table was begun by bsgs_kangaroo_dptable_begin%s: it holds the ids of one engine", (*k)->dpt_keyed ? "_keys" : "");
+        return BSGS_OK;
+    }
     if (d && d->kangaroo && d->kangaroo->dpt.tag && d->kangaroo->dpt_keyed && table) {
         *k = d->kangaroo;
         if (want == DPT_UNKEYED)
@@ -246,10 +263,11 @@ static int dpt_herd(bsgs_dev *d, bsgs_kangaroo **k, bool table, int want = DPT_U
 }
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
-int bsgs_kang_dpt_begin(bsgs_dev *d, uint64_t capacity, bool keyed)
+int bsgs_kang_dpt_begin(bsgs_dev *d, uint64_t capacity, int kind)
 {
+    const bool keyed = kind == DPT_KEYED;
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, false, keyed ? DPT_KEYED : DPT_UNKEYED)) return rc;
+    if (int rc = dpt_herd(d, &k, false, kind)) return rc;
     if (!capacity || capacity > KT_MAX_CAPACITY) return fail(BSGS_ERR_ARG, "distinguished-point table of %llu entries: 1..2^31", (unsigned long long)capacity);
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -268,19 +286,19 @@ int bsgs_kang_dpt_begin(bsgs_dev *d, uint64_t capacity, bool keyed)
     return BSGS_OK;
 }
 
-extern "C" int bsgs_kangaroo_dptable_begin(bsgs_dev *d, uint64_t capacity) { return bsgs_kang_dpt_begin(d, capacity, false); }
+extern "C" int bsgs_kangaroo_dptable_begin(bsgs_dev *d, uint64_t capacity) { return bsgs_kang_dpt_begin(d, capacity, DPT_UNKEYED); }
 
-int bsgs_kang_dpt_run(bsgs_dev *d, bool keyed, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen, uint64_t *n_entries,
-                      uint64_t *dropped, float *kernel_ms)
+int bsgs_kang_dpt_run(bsgs_dev *d, int kind, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen, uint64_t *n_entries,
+                      uint64_t *dropped, float *kernel_ms, const DptRouted *rt)
 {
     if (!d || !nrecs) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, true, keyed ? DPT_KEYED : DPT_UNKEYED)) return rc;
+    if (int rc = dpt_herd(d, &k, true, kind)) return rc;
     HIPCHK(hipSetDevice(d->id));
     HIPCHK(hipMemsetAsync(k->dpt_out, 0, KANG_REC_HEADER, d->stream));
     if (int rc = bsgs_kangaroo_launch(d, steps)) return rc;          // the walk, timed from ev0
-    if (int rc = dpt_insert(d, k)) return rc;
-    uint64_t count = 0, places = 0, back = 0;
+    if (int rc = dpt_insert(d, k, rt ? rt->base : 0u)) return rc;
+    uint64_t count = 0, places = 0, back = 0, cut = 0;
     if (int rc = bsgs_kangaroo_finish(d, &count, k->dpt_out, &places, kernel_ms)) return rc;      // ev1 behind the resolve, both counts, the synchronisation
     HIPCHK(hipMemcpyAsync(&back, (const char *)k->dpt_out + 8, 8, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -290,45 +308,47 @@ int bsgs_kang_dpt_run(bsgs_dev *d, bool keyed, uint32_t steps, bsgs_kangaroo_rec
     uint32_t give = 0;
     uint64_t kept = 0;
     if (int rc = dpt_copy_out(d, k, places, recs, max_recs, &give, &kept)) return rc;
+    if (rt) if (int rc = bsgs_kang_dpt_routed_out(d, k, held, rt, &cut)) return rc;
     if (int rc = bsgs_kang_table_entries(d, &k->dpt, n_entries)) return rc;
     *nrecs = give;
     if (n_seen) *n_seen = count;
-    if (dropped) *dropped = (count - held) + (back - kept);          // never inserted, and handed back but not handed over (a pair counts once)
+    if (dropped) *dropped = (count - held) + (back - kept) + cut;    // never inserted, handed back but not handed over (a pair counts once), routed but cut
     return BSGS_OK;
 }
 
 extern "C" int bsgs_kangaroo_run_dptable(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen,
                                          uint64_t *n_entries, uint64_t *dropped, float *kernel_ms)
 {
-    return bsgs_kang_dpt_run(d, false, steps, recs, max_recs, nrecs, n_seen, n_entries, dropped, kernel_ms);
+    return bsgs_kang_dpt_run(d, DPT_UNKEYED, steps, recs, max_recs, nrecs, n_seen, n_entries, dropped, kernel_ms);
 }
 
-int bsgs_kang_dpt_insert(bsgs_dev *d, bool keyed, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs, uint32_t *nrecs,
-                         uint64_t *n_entries, uint64_t *dropped)
+int bsgs_kang_dpt_insert(bsgs_dev *d, int kind, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs, uint32_t *nrecs,
+                         uint64_t *n_entries, uint64_t *dropped, const DptRouted *rt)
 {
     if (!d || !nrecs || (n && !recs_in)) return fail(BSGS_ERR_ARG, "null");
     bsgs_kangaroo *k = nullptr;
-    if (int rc = dpt_herd(d, &k, true, keyed ? DPT_KEYED : DPT_UNKEYED)) return rc;
+    if (int rc = dpt_herd(d, &k, true, kind)) return rc;
     const uint64_t count = n;
     if (int rc = bsgs_kang_table_stage(d, k, k->dpt_out, recs_in, &count)) return rc;
-    if (int rc = dpt_insert(d, k)) return rc;
+    if (int rc = dpt_insert(d, k, rt ? rt->base : 0u)) return rc;
     uint64_t head[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(head, k->dpt_out, 16, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     const uint64_t back = std::min<uint64_t>(head[1], n);
     const uint64_t places = std::min<uint64_t>(head[0], std::min<uint64_t>(2 * back, dpt_out_cap(k)));
     uint32_t give = 0;
-    uint64_t kept = 0;
+    uint64_t kept = 0, cut = 0;
     if (int rc = dpt_copy_out(d, k, places, recs_out, max_recs, &give, &kept)) return rc;
+    if (rt) if (int rc = bsgs_kang_dpt_routed_out(d, k, n, rt, &cut)) return rc;
     *nrecs = give;
-    if (dropped) *dropped = back - kept;
+    if (dropped) *dropped = back - kept + cut;
     return bsgs_kang_table_entries(d, &k->dpt, n_entries);
 }
 
 extern "C" int bsgs_kangaroo_dptable_insert(bsgs_dev *d, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs,
                                             uint32_t *nrecs, uint64_t *n_entries, uint64_t *dropped)
 {
-    return bsgs_kang_dpt_insert(d, false, recs_in, n, recs_out, max_recs, nrecs, n_entries, dropped);
+    return bsgs_kang_dpt_insert(d, DPT_UNKEYED, recs_in, n, recs_out, max_recs, nrecs, n_entries, dropped);
 }
 
 extern "C" int bsgs_kangaroo_dptable_load(bsgs_dev *d, const bsgs_kangaroo_dp_entry *entries, uint64_t n, uint64_t *n_stored, uint64_t *n_duplicate, uint64_t *n_zero,

@@ -92,16 +92,16 @@ int bsgs_kang_dpt_insert_keys_launch(bsgs_dev *d, bsgs_kangaroo *k, uint32_t blo
 }
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------------------------
-extern "C" int bsgs_kangaroo_dptable_begin_keys(bsgs_dev *d, uint64_t capacity) { return bsgs_kang_dpt_begin(d, capacity, true); }
+extern "C" int bsgs_kangaroo_dptable_begin_keys(bsgs_dev *d, uint64_t capacity) { return bsgs_kang_dpt_begin(d, capacity, BSGS_DPT_KEYED); }
 
 extern "C" int bsgs_kangaroo_run_dptable_keys(bsgs_dev *d, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t max_recs, uint32_t *nrecs, uint64_t *n_seen,
                                               uint64_t *n_entries, uint64_t *dropped, float *kernel_ms)
 {
-    return bsgs_kang_dpt_run(d, true, steps, recs, max_recs, nrecs, n_seen, n_entries, dropped, kernel_ms);
+    return bsgs_kang_dpt_run(d, BSGS_DPT_KEYED, steps, recs, max_recs, nrecs, n_seen, n_entries, dropped, kernel_ms);
 }
 
 extern "C" int bsgs_kangaroo_dptable_insert_keys(bsgs_dev *d, const bsgs_kangaroo_record *recs_in, uint32_t n, bsgs_kangaroo_record *recs_out, uint32_t max_recs,
                                                  uint32_t *nrecs, uint64_t *n_entries, uint64_t *dropped)
 {
-    return bsgs_kang_dpt_insert(d, true, recs_in, n, recs_out, max_recs, nrecs, n_entries, dropped);
+    return bsgs_kang_dpt_insert(d, BSGS_DPT_KEYED, recs_in, n, recs_out, max_recs, nrecs, n_entries, dropped);
 }

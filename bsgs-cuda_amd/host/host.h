@@ -233,6 +233,9 @@ int kangaroo_selftest(const std::vector<std::string> &args);
 int kangaroo_work_selftest(const std::vector<std::string> &args);
 int kangaroo_roundtrip_selftest(const std::vector<std::string> &args);
 int kangaroo_dpdev_selftest(const std::vector<std::string> &args);               // -selftest kangaroo-dpdev [sym]: the hand-back rule of -kdpdev on scripted records and pairs
+int kangaroo_dpshard_selftest(const std::vector<std::string> &args);             // -selftest kangaroo-dpshard [sym] <engines> <kn>: the hand-back rule of -kdpshard, kangaroo numbers global
+int kangaroo_barrier_selftest(const std::vector<std::string> &args);             // -selftest kangaroo-barrier <event>...: -kdpshard's barrier before a save, scripted
+int kangaroo_dpshard_plan_selftest(const std::vector<std::string> &args);        // -selftest kangaroo-dpshard-plan: the plan of -kdpshard for E engines
 int kangaroo_dpkeys_selftest(const std::vector<std::string> &args);              // -selftest kangaroo-dpkeys [sym]: the hand-back rule of -kdpkeys on scripted records and pairs
 int kangaroo_dpkeys_sym_selftest(const std::vector<std::string> &args);          // ... its part for the symmetric walk's table (host_kangaroo_symlist.cpp)
 int kangaroo_dpkeys_plan_selftest(const std::vector<std::string> &args);         // -selftest kangaroo-dpkeys-plan: the plan of -kdpkeys (dp, herd, launch, record buffer, capacity)

@@ -85,7 +85,10 @@ void usage(const Config &c)
            "-kdpdev      Kangaroo -pb, plain and -ksym (one -d entry): distinguished points are kept and paired in GPU memory; only collisions, dead kangaroos and cycles cross the bus,\n"
            "             so the default plan is a low -dp and the full herd; kangaroo.work is the same file with and without the flag (not with -infile, -ktames*, -ktamesgen);\n"
            "             without -d it runs on GPU #0; every save (-wt, and the last) reads the whole table: 32 bytes per entry of GPU memory for the read and of host memory for the file\n"
-           "-kdpn N      Kangaroo -kdpdev / -kdpkeys: entries the table in GPU memory is sized for, 1..2^31, 64 bytes each (default: the power of two at or above 4 sqrt(width), 2^16..2^27;\n"
+           "-kdpshard    Kangaroo -pb, plain and -ksym: -kdpdev's table divided over the engines of -d by tag, each share kept and paired in its engine's GPU memory; records that belong to\n"
+           "             another engine's share are relayed to it (without -d: every GPU; -d 0,0 runs two engines on one GPU; -kdpn: entries per engine; kangaroo.work is the plain\n"
+           "             multi-engine file, resumable with and without the flag on the same number of -d entries; not with -kdpdev, -kdpkeys, -infile, -ktames*)\n"
+           "-kdpn N      Kangaroo -kdpdev / -kdpkeys / -kdpshard: entries the table in GPU memory is sized for, 1..2^31, 64 bytes each (default: the power of two at or above 4 sqrt(width), 2^16..2^27;\n"
            "             -kdpkeys: 4 sqrt(open keys x width))\n"
            "-kdpkeys     Kangaroo -infile, plain and -kwalk sym (one -d entry): the list search's distinguished points are kept in GPU memory with the key that owns each and paired there;\n"
            "             only collisions, dead kangaroos and cycles cross the bus.  The plan is -kdpdev's with sqrt(open keys x width) in the place of sqrt(width); kangaroo.work is the same\n"
@@ -158,7 +161,7 @@ Config parse_args(int argc, char **argv)
         else if (a == "-hostcentres") c.host_centres = true;
         else if (a == "-tune") c.tune = true;
         else if (a == "-joblog") c.joblog = next();
-        else if (a == "-kdpdev" || a == "-kdpn" || a == "-kdpkeys") die(a + " belongs to -kangaroo (the table of distinguished points of a kangaroo search, kept in GPU memory)");
+        else if (a == "-kdpdev" || a == "-kdpn" || a == "-kdpkeys" || a == "-kdpshard") die(a + " belongs to -kangaroo (the table of distinguished points of a kangaroo search, kept in GPU memory)");
         else die("Unknown parameter " + a);
     }
     // limits 1_9_7File.pb:4412-4418, 4616-4618

@@ -162,7 +162,8 @@ bool parse_range_pub(const std::string &pk, const std::string &pke, const std::s
 // one scripted record (T|W|D,<x hex>,<d hex>,<kangaroo>; sym: also N, a wild kangaroo with NEG, and C, a cycle's dead record) into the table: prints the
 // verdict line of -selftest kangaroo.  dpt (-selftest kangaroo-dpdev): the record goes through DevDpTable::take as the device would hand it back -- paired: as
 // the duplicate behind the stored half taken before it, never a dead record -- and is judged as take() names it
-bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = false, DevDpTable *dpt = nullptr, bool paired = false)
+// kn (-selftest kangaroo-dpshard): the kangaroo numbers are global, and a re-seed names the engine and the index there: "reseed <engine> <index>"
+bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = false, DevDpTable *dpt = nullptr, bool paired = false, uint64_t kn = 0)
 {
     const std::vector<std::string> f = split_commas(rec);
     if (f.size() != 4 || f[0].size() != 1 || !strchr(paired ? (sym ? "TWN" : "TW") : (sym ? "TWDNC" : "TWD"), f[0][0])) return false;
@@ -187,7 +188,10 @@ bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = fals
     switch (v) {
     case KangarooTable::NEW: printf("new\n"); break;
     case KangarooTable::FOUND: printf("found %s\n", hs::fe_to_hex(key).c_str()); break;
-    case KangarooTable::RESEED: printf("reseed %s\n", f[3].c_str()); break;
+    case KangarooTable::RESEED:
+        if (kn) printf("reseed %llu %llu\n", (unsigned long long)(r.kangaroo / kn), (unsigned long long)(r.kangaroo % kn));
+        else printf("reseed %s\n", f[3].c_str());
+        break;
     case KangarooTable::FALSE_MATCH: printf("false\n"); break;
     case KangarooTable::REPEAT: printf("repeat\n"); break;
     }
@@ -201,7 +205,7 @@ bool scripted_record(KangarooTable &tab, const std::string &rec, bool sym = fals
 // -selftest kangaroo-dpdev [sym] <pk hex> <pke hex> <pubkey> <item>...: the hand-back rule of -kdpdev without a GPU, every item through DevDpTable::take.  An
 // item is a scripted record as above -- what the device hands back alone: DEAD, tag 0, a full table -- and goes through the host's own map; or
 // S,<tag hex>,<d hex>,<kangaroo>,<type> followed by its record: a duplicate, judged against the stored entry it came with.  The same verdict and summary lines.
-static int table_selftest(const std::vector<std::string> &a, bool sym, bool dpdev)
+static int table_selftest(const std::vector<std::string> &a, bool sym, bool dpdev, uint64_t kn = 0)
 {
     if (a.size() < 3) return 2;
     Scalar lo, hi; Affine P; u128 W;
@@ -210,7 +214,7 @@ static int table_selftest(const std::vector<std::string> &a, bool sym, bool dpde
     DevDpTable dpt;
     dpt.on = dpdev;
     if (!dpt.scripted_items(a, [&](const std::string &rec, bool paired) {
-            return !(paired && dpt.half.flags > 1u && !(sym && dpt.half.flags == 3u)) && scripted_record(tab, rec, sym, &dpt, paired); })) return 2;
+            return !(paired && dpt.half.flags > 1u && !(sym && dpt.half.flags == 3u)) && scripted_record(tab, rec, sym, &dpt, paired, kn); })) return 2;
     if (sym) printf("summary %zu %llu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds(), (unsigned long long)tab.cycles());
     else printf("summary %zu %llu %llu\n", tab.size(), (unsigned long long)tab.false_matches(), (unsigned long long)tab.reseeds());
     return 0;
@@ -221,6 +225,67 @@ int kangaroo_dpdev_selftest(const std::vector<std::string> &a)
 {
     const bool sym = !a.empty() && a[0] == "sym";
     return table_selftest(sym ? std::vector<std::string>(a.begin() + 1, a.end()) : a, sym, true);
+}
+
+// -selftest kangaroo-dpshard [sym] <engines> <kn> <pk hex> <pke hex> <pubkey> <item>...: the items of kangaroo-dpdev as the E tables of -kdpshard hand them back,
+// every kangaroo number global (engine * kn + index); the same verdict lines, but a re-seed names its engine and the index there
+int kangaroo_dpshard_selftest(const std::vector<std::string> &a)
+{
+    const bool sym = !a.empty() && a[0] == "sym";
+    const std::vector<std::string> b(a.begin() + (sym ? 1 : 0), a.end());
+    if (b.size() < 5) return 2;
+    const uint64_t engines = strtoull(b[0].c_str(), nullptr, 10), kn = strtoull(b[1].c_str(), nullptr, 10);
+    if (!engines || engines > BSGS_KANGAROO_DPT_MAX_SHARDS || !kn) return 2;
+    for (size_t i = 5; i < b.size(); i++) {                            // every kangaroo an item names is one of the engines'
+        const std::vector<std::string> f = split_commas(b[i]);
+        if (f.size() >= 4 && strtoull(f[3].c_str(), nullptr, 10) >= engines * kn) return 2;
+    }
+    return table_selftest(std::vector<std::string>(b.begin() + 2, b.end()), sym, true, kn);
+}
+// -selftest kangaroo-barrier <event>...: the barrier in front of the last drain before a save (SaveBarrier, host_kangaroo_run.h) without threads or a GPU.
+// Two engines, A and B; events: open (the saver opens a save round and asks), withdraw (it takes the request back), stop, A / B (the engine arrives: in the
+// stop round when stop has been said, else in the save round), exitA / exitB (the engine's thread ends).  After every event one line: the state of each engine
+// that waits, "A=<wait|all|given-up> B=...", "-" for one that does not; an engine that passes (all) or is let go (given-up) waits no longer and may arrive again
+int kangaroo_barrier_selftest(const std::vector<std::string> &a)
+{
+    SaveBarrier b;
+    bool save_req = false, stop = false, waits[2] = {false, false}, stopped[2] = {false, false};
+    uint64_t round[2] = {0, 0};
+    uint32_t living = 2;
+    const char *names[] = {"wait", "all", "given-up"};
+    for (const std::string &ev : a) {
+        if (ev == "open") { b.open(); save_req = true; }
+        else if (ev == "withdraw") save_req = false;
+        else if (ev == "stop") stop = true;
+        else if (ev == "A" || ev == "B") { const int e = ev == "B"; if (waits[e]) return 2; stopped[e] = stop; round[e] = b.arrive(stop); waits[e] = true; }
+        else if (ev == "exitA" || ev == "exitB") { if (!living) return 2; living--; waits[ev == "exitB"] = false; }
+        else return 2;
+        std::string line;
+        for (int e = 0; e < 2; e++) {
+            const SaveBarrier::State st = b.state(stopped[e], round[e], living, save_req, stop);
+            line += std::string(e ? " B=" : "A=") + (waits[e] ? names[st] : "-");
+            if (waits[e] && st != SaveBarrier::WAIT) waits[e] = false;      // it passes, or it is let go
+        }
+        printf("%s\n", line.c_str());
+    }
+    return 0;
+}
+
+// -selftest kangaroo-dpshard-plan <pk hex> <pke hex> <CUs> <min launch> <dp or -1> <kn or 0> <kdpn or 0> <engines>: the plan of -kdpshard without a GPU, one
+// line: "plan <dp> <kn> <per thread> <S> <record buffer> <capacity per engine> <engines>"; with 1 engine the numbers of kangaroo-dpdev-plan
+int kangaroo_dpshard_plan_selftest(const std::vector<std::string> &a)
+{
+    if (a.size() != 8) return 2;
+    KangConfig c;
+    c.pk = a[0]; c.pke = a[1]; c.dp = atoi(a[4].c_str()); c.kdpn = strtoull(a[6].c_str(), nullptr, 0);
+    Prologue p(c);
+    const uint32_t engines = (uint32_t)strtoul(a[7].c_str(), nullptr, 10);
+    if (!engines || engines > BSGS_KANGAROO_DPT_MAX_SHARDS) { fprintf(stderr, "kangaroo-dpshard-plan: %s engines, a table is divided over 1..16\n", a[7].c_str()); return 2; }
+    DevDpTable dpt;
+    Plan pl = plan_herd(p.sqrtW, engines, atoi(a[2].c_str()), dpt.plan(c, p.sqrtW, 0, engines), strtoull(a[5].c_str(), nullptr, 0));
+    plan_launch(pl, p.sqrtW, 0.0, atof(a[3].c_str()), true, c.dp < 0);
+    printf("plan %u %llu %u %u %u %llu %u\n", pl.dp, (unsigned long long)pl.kn, pl.G, pl.S, pl.cap, (unsigned long long)dpt.capacity, engines);
+    return 0;
 }
 
 // -selftest kangaroo-dpdev-plan <pk hex> <pke hex> <CUs> <min launch> <dp or -1> <kn or 0> <kdpn or 0>: the plan of -kdpdev for one engine without a GPU, one line:
@@ -311,6 +376,7 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else if (a == "-kcpuseed") c.cpuseed = true;
         else if (a == "-kdpdev") c.kdpdev = true;
         else if (a == "-kdpkeys") c.kdpkeys = true;
+        else if (a == "-kdpshard") c.kdpshard = true;
         else if (a == "-kdpn") { c.kdpn = strtoull(next().c_str(), nullptr, 0); if (!c.kdpn || c.kdpn > (1ull << 31)) die("-kdpn must be 1..2^31"); }
         else if (a == "-ksym") ksym = true;
         else if (a == "-kwalk") { const std::string w = next(); if (w != "plain" && w != "sym") die("-kwalk must be plain or sym"); kwalk_sym = w == "sym"; }
@@ -321,7 +387,15 @@ KangConfig kang::parse_kangaroo_args(int argc, char **argv)
         else die("Unknown parameter with -kangaroo: " + a);
     }
     // -kdpdev: the table of distinguished points of the one-key search, plain and -ksym, in device memory; every refusal before any device is looked for
-    if (c.kdpn && !c.kdpdev && !c.kdpkeys) die("-kdpn belongs to -kdpdev or -kdpkeys (the capacity of the table in GPU memory)");
+    if (c.kdpn && !c.kdpdev && !c.kdpkeys && !c.kdpshard) die("-kdpn belongs to -kdpdev or -kdpkeys, or to -kdpshard (the capacity of the table in GPU memory)");
+    // -kdpshard: that table divided over the engines of -d (without -d: every GPU, as plain -kangaroo), -kdpn entries on each
+    if (c.kdpshard) {
+        if (c.kdpdev) die("-kangaroo -kdpshard cannot be combined with -kdpdev (-kdpdev is one table on one engine, -kdpshard one table divided over the engines of -d)");
+        if (c.kdpkeys) die("-kangaroo -kdpshard cannot be combined with -kdpkeys (the table of a key list stays on one engine)");
+        if (!c.infile.empty()) die("-kangaroo -kdpshard cannot be combined with -infile (the divided table pairs the records of one key)");
+        if (!c.ktames.empty() || !c.ktamesgen.empty() || !c.ktamesmerge.empty() || c.ktamesdev || !c.ktamesfrom.empty() || c.ktnplan || c.ktn)
+            die("-kangaroo -kdpshard cannot be combined with -ktames, -ktamessym, -ktamesgen or their flags (a tame table is matched or grown by calls of its own)");
+    }
     // one engine with one table: one -d entry; without -d a run takes every GPU of the machine, here it takes the first
     auto one_engine = [&c](const std::string &flag) {
         if (c.devices.find(',') != std::string::npos) die("-kangaroo " + flag + " takes one -d entry (several engines would need one table for all of them)");
@@ -439,6 +513,7 @@ struct KeyMode : Mode {
         printf("Kangaroo range [%s, %s], width 2^%.2f\n", hs::fe_to_hex(p.lo).c_str(), hs::fe_to_hex(p.hi).c_str(), std::log2((double)p.W));
         if (c.kdpdev && p.resume && f.engines != 1) die("Recovery file was made with other settings");      // (-kdpdev is one engine with one table)
         if (c.kdpdev) dp_fixed = dpt.plan(c, p.sqrtW, p.resume ? f.table : 0);
+        if (c.kdpshard && p.resume && f.engines > BSGS_KANGAROO_DPT_MAX_SHARDS) die("Recovery file was made with other settings");
         // -ksym: offsets are counted from the middle of the range, k'' = k - (a + W/2) (include/bsgs_hip.h "Kangaroo, symmetric walk")
         base = c.sym ? hs::sc_add(p.lo, hs::sc_from_u128(p.W / 2)) : p.lo;
         Q = hs::point_add(P, hs::affine_neg(hs::point_mul(hs::G, base)));
@@ -452,6 +527,13 @@ struct KeyMode : Mode {
         printf("\nFindpubkey  : %s\n", hs::compress_pubkey(P).c_str());
         return true;
     }
+    // -kdpshard: the engines are known, so is each one's share of the table, and with it dp
+    void engines_known(Prologue &p) override
+    {
+        if (!c.kdpshard) return;
+        if (p.gpus.size() > BSGS_KANGAROO_DPT_MAX_SHARDS) die("-kangaroo -kdpshard takes at most 16 engines");
+        dp_fixed = dpt.plan(c, p.sqrtW, p.resume ? p.wf.h.table : 0, (uint32_t)p.gpus.size());
+    }
     // after the prologue: the table (-wl: the file's), the offsets of the initial herds in engine order from the seeded stream, whoever computes the points,
     // and with the host's comb the herds themselves, on up to 16 threads, before any engine starts
     void prepare(Prologue &p, Shared &sh)
@@ -459,7 +541,7 @@ struct KeyMode : Mode {
         table.reset(new KangarooTable(p.lo, p.W, P, c.sym));
         if (p.resume) {
             const bool sym = c.sym;                                    // the type words of a table entry: 0 tame, 1 wild, -ksym: 3 wild with NEG
-            if (c.kdpdev && !dpt.split(p.wf.table, [sym](uint32_t type) { return type <= 1u || (sym && type == 3u); })) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
+            if (dpt.on && !dpt.split(p.wf.table, [sym](uint32_t type) { return type <= 1u || (sym && type == 3u); })) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
             if (!table->restore(p.wf.table.data(), p.wf.table.size() / 32, p.wf.h.false_matches, p.wf.h.reseeds)) die("-kangaroo -wl: the table section of " + p.wl_path + " does not load");
             std::vector<uint8_t>().swap(p.wf.table);
             table->set_cycles(p.wf.h.cycles);
@@ -515,15 +597,21 @@ struct KeyMode : Mode {
         const Plan &pl = pro->pl;
         if ((c.sym ? bsgs_kangaroo_setup_sym(dev, pro->jxy.data(), pro->js.data(), jumps, pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)
                    : bsgs_kangaroo_setup(dev, pro->jxy.data(), pro->js.data(), pl.dp, (uint32_t)pl.kn, pl.G, pl.cap)) != BSGS_OK) return "bsgs_kangaroo_setup";
-        return dpt.begin(dev);
+        return dpt.sharded ? nullptr : dpt.begin(dev);
     }
+    const char *setup_engine(bsgs_dev *dev, uint32_t e) override      // -kdpshard: engine e's share of the table
+    {
+        const char *failed = setup(dev);
+        return failed || !dpt.sharded ? failed : dpt.begin(dev, e);
+    }
+    std::string drain(bsgs_dev *dev, uint32_t e, Shared &sh) override { return dpt.drain(dev, e, sh); }
     // -kdpdev: the launch, the load at -wl and the read for a save are the device table's
     int launch(bsgs_dev *dev, uint32_t e, uint32_t steps, bsgs_kangaroo_record *recs, uint32_t cap, uint32_t *n, uint64_t *dropped, Shared &sh) override
     {
-        return dpt.on ? dpt.launch(dev, steps, recs, cap, n, dropped, sh) : Mode::launch(dev, e, steps, recs, cap, n, dropped, sh);
+        return dpt.on ? dpt.launch(dev, steps, recs, cap, n, dropped, sh, e) : Mode::launch(dev, e, steps, recs, cap, n, dropped, sh);
     }
-    std::string resumed(bsgs_dev *dev, uint32_t, Shared &) override { return dpt.resumed(dev, pro->wl_path); }
-    std::string fetch(bsgs_dev *dev, uint32_t, Shared &) override { return dpt.fetch(dev); }
+    std::string resumed(bsgs_dev *dev, uint32_t e, Shared &) override { return dpt.resumed(dev, pro->wl_path, e); }
+    std::string fetch(bsgs_dev *dev, uint32_t e, Shared &) override { return dpt.fetch(dev, e); }
     size_t table_size() const { return table->size() + (size_t)dpt.entries.load(); }      // "in the table": the host's entries and the device's
     // (a whole herd from the host's comb was computed in prepare() and is uploaded by the driver: the comb is asked for lists only)
     const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) override
@@ -554,7 +642,7 @@ struct KeyMode : Mode {
         u128 d;
         memcpy(&d, r.d, 16);
         Scalar k;
-        const uint32_t kid = (uint32_t)(e * pro->pl.kn + r.kangaroo);
+        const uint32_t kid = dpt.sharded ? r.kangaroo : (uint32_t)(e * pro->pl.kn + r.kangaroo);      // -kdpshard: the device's ids are global already
         KangarooTable::Verdict v;
         const DevDpTable::Taken t = dpt.take(r);
         u128 ed;
@@ -564,7 +652,10 @@ struct KeyMode : Mode {
         default: v = table->add(r.x, d, kid, r.flags, &k);             // no -kdpdev, or what the device hands back alone: the host's own map
         }
         if (v == KangarooTable::FOUND) { key = k; found = true; sh.stop = true; return false; }
-        if (v == KangarooTable::RESEED) sh.push_reseed(e, r.kangaroo);
+        if (v == KangarooTable::RESEED) {
+            if (dpt.sharded) sh.push_reseed((uint32_t)(kid / pro->pl.kn), (uint32_t)(kid % pro->pl.kn));      // (an inbox record belongs to the engine it came from)
+            else sh.push_reseed(e, r.kangaroo);
+        }
         return true;
     }
     uint32_t entry_flags(uint32_t type) const override { return (type & 1u ? BSGS_KANGAROO_WILD : 0u) | (type & 2u ? BSGS_KANGAROO_NEG : 0u); }      // 0 tame, 1 wild, 3 wild with NEG
@@ -613,7 +704,8 @@ int kangaroo_main(int argc, char **argv)
     p.complete(c, mode);
     const Plan &pl = p.pl;
     printf("Expected steps: 2^%.2f (2 sqrt(W) + DP overhead), expected DPs 2^%.2f\n", std::log2(pl.expected), std::log2(2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) + 1.0));
-    if (c.kdpdev) mode.dpt.banner(pl.cap);
+    if (c.kdpshard) mode.dpt.shards(pl.engines, pl.kn, pl.cap);
+    if (c.kdpdev || c.kdpshard) mode.dpt.banner(pl.cap);
     else if (c.dp < 0 && 2.0 * p.sqrtW / std::ldexp(1.0, (int)pl.dp) > 67108864.0) printf("WARNING: the expected DP count exceeds 2^26 host entries even at -dp 32\n");
     if (c.sym) printf("Kangaroo: symmetric walk (negation map), %u jump points, jump scale %g\n", p.wh.jumps, p.wh.jumpscale);
     Shared sh(p);
@@ -638,7 +730,9 @@ int kangaroo_main(int argc, char **argv)
              (unsigned long long)table.reseeds());
     text += tail;
     if (c.sym) text += "Symmetric walk: " + std::to_string(table.cycles()) + " cycles retired\n";
-    for (uint32_t e = 0; e < pl.engines; e++) text += "Engine " + std::to_string(e) + " (GPU #" + std::to_string(p.gpus[e]) + "): " + std::to_string(sh.engine_records[e]) + " records\n";
+    for (uint32_t e = 0; e < pl.engines; e++)
+        text += "Engine " + std::to_string(e) + " (GPU #" + std::to_string(p.gpus[e]) + "): " + std::to_string(sh.engine_records[e]) + " records" +
+                (c.kdpshard ? ", " + std::to_string(sh.routed[e].load()) + " routed to other engines" : std::string()) + "\n";
     fputs(text.c_str(), stdout);                                       // one lane: the JobList leaves the console to the job (it appends win.txt)
     mode.jobs->finish(0, text, o == DONE, win);
     printf("Found %d of %zu\n", mode.jobs->found(), mode.jobs->size());

@@ -82,6 +82,7 @@ struct KangConfig {
     bool range_given = false;                      // -pk or -pke stood on the command line
     bool kdpdev = false;                           // -kdpdev with -pb, plain and -ksym: the table of distinguished points lives in device memory (bsgs_kangaroo_run_dptable)
     uint64_t kdpn = 0;                             // -kdpn N with -kdpdev or -kdpkeys: the capacity of that table (default: dpdev_capacity)
+    bool kdpshard = false;                         // -kdpshard with -pb, plain and -ksym: that table divided over the engines of -d, each share in its engine's memory (bsgs_kangaroo_run_dptable_shard)
     bool kdpkeys = false;                          // -kdpkeys with -infile, plain and -kwalk sym: the list search's table lives in device memory (bsgs_kangaroo_run_dptable_keys)
 };
 KangConfig parse_kangaroo_args(int argc, char **argv);

@@ -107,6 +107,7 @@ void Prologue::complete(const KangConfig &c, Mode &mode)
     if (resume && gpus.size() != wf.h.engines) die("Recovery file was made with other settings");
     int cus = 256;
     { bsgs_dev *d = nullptr; CK(bsgs_dev_open(gpus[0], &d)); bsgs_dev_cu_count(d, &cus); bsgs_dev_close(d); }
+    mode.engines_known(*this);
     // defaults from W (plan_herd); then the expected total, the launch length and the record buffer, which depend on it
     pl = plan_herd(sqrtW, (uint32_t)gpus.size(), cus, resume ? (int)wf.h.dp : mode.dp_fixed >= 0 ? mode.dp_fixed : c.dp, c.kn);
     if (resume) { pl.kn = wf.h.herd; pl.G = wf.h.per_thread; }        // the plan of the run that saved, not this GPU's
@@ -144,7 +145,9 @@ void Prologue::complete(const KangConfig &c, Mode &mode)
 
 Shared::Shared(const Prologue &p) : rng(p.rng), reseed(p.pl.engines), engine_records(p.pl.engines, 0), saved(p.pl.engines)
 {
-    for (uint32_t e = 0; e < p.pl.engines; e++) reseed_m.emplace_back(new std::mutex);
+    for (uint32_t e = 0; e < p.pl.engines; e++) { reseed_m.emplace_back(new std::mutex); inbox.emplace_back(new Inbox); }
+    routed.reset(new std::atomic<uint64_t>[p.pl.engines]);
+    for (uint32_t e = 0; e < p.pl.engines; e++) routed[e] = 0;
     if (p.resume) {
         steps = p.wf.h.steps; dps = p.wf.h.dps; dropped = p.wf.h.dropped;
         reseed = p.wf.reseed;
@@ -218,7 +221,7 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
     };
     const char *failed = nullptr;
     if (bsgs_dev_open(p.gpus[e], &dev) != BSGS_OK) failed = "bsgs_dev_open";
-    else if ((failed = mode.setup(dev)) != nullptr) {}
+    else if ((failed = mode.setup_engine(dev, e)) != nullptr) {}
     else if (!p.herds[e].empty()) {
         if (bsgs_kangaroo_upload(dev, 0, (uint32_t)kn, p.herds[e].data()) != BSGS_OK) failed = "bsgs_kangaroo_upload";
         std::vector<bsgs_kangaroo_state>().swap(p.herds[e]);
@@ -269,6 +272,7 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
                 if ((failed = mode.seed(dev, e, rs, sh)) != nullptr) { bad(failed); break; }
             }
         }
+        if (!sh.stop.load() && mode.sharded) { const std::string msg = mode.drain(dev, e, sh); if (!msg.empty()) { end_with(msg); break; } }
         if (!sh.stop.load()) {
             uint32_t n = 0;
             uint64_t dropped = 0;
@@ -285,6 +289,24 @@ void engine(uint32_t e, const KangConfig &c, Prologue &p, Shared &sh, Mode &mode
         const bool stopped = sh.stop.load();
         bool want = sh.save_req.load();
         if (stopped) { std::lock_guard<std::mutex> lt(sh.tab_m); want = mode.saves && !mode.done(); }
+        // -kdpshard: a routed record that reached no table at a save would be lost for good (a kangaroo records a point once).  So no engine drains its
+        // last inbox before every living engine has made its last launch and pushed what it routed; then each drains, and only then checks, downloads and
+        // fetches.  The barrier counts the living engines and gives way to a failure and to a found key (nothing is saved then).  A save round that is
+        // given up while an engine waits in it (a signal withdraws the request, a stop comes) lets that engine go on: it meets the others in the stop round
+        if (want && mode.sharded && !sh.failed.load()) {
+            uint64_t round;
+            { std::lock_guard<std::mutex> lk(sh.save_m); round = sh.barrier.arrive(stopped); }
+            SaveBarrier::State st = SaveBarrier::WAIT;
+            for (;;) {
+                { std::lock_guard<std::mutex> lk(sh.save_m); st = sh.barrier.state(stopped, round, sh.running, sh.save_req.load(), sh.stop.load()); }
+                if (st != SaveBarrier::WAIT || sh.failed.load()) break;
+                { std::lock_guard<std::mutex> lt(sh.tab_m); if (mode.done()) break; }
+                std::this_thread::sleep_for(std::chrono::milliseconds(1));
+            }
+            if (st == SaveBarrier::GIVEN_UP) continue;
+            const bool all = st == SaveBarrier::ALL;
+            if (all) { const std::string msg = mode.drain(dev, e, sh); if (!msg.empty()) { end_with(msg); break; } }
+        }
         if (want && check && !sh.failed.load()) {                      // before every save: a herd that went wrong never replaces a good file
             const auto ts = Clock::now();
             uint32_t at = 0;
@@ -320,7 +342,9 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
 {
     const Plan &pl = p.pl;
     // the work file from the state as it stands: callers make sure that no engine walks and the collector's queue is empty
-    auto write_state = [&]() {
+    // false: refused -- under -kdpshard a state with a routed record in an inbox is not a cut of the search
+    auto write_state = [&]() -> bool {
+        if (mode.sharded && !sh.inboxes_empty()) { fprintf(stderr, "\nWARNING: save refused, routed records wait in an inbox: %s left as it was\n", p.work_path.c_str()); return false; }
         std::lock_guard<std::mutex> lt(sh.tab_m);
         WorkHeader h = p.wh;
         h.rng = sh.rng; h.steps = sh.steps.load(); h.dps = sh.dps.load(); h.dropped = sh.dropped.load();
@@ -331,6 +355,7 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
         std::vector<std::vector<uint32_t>> rs(pl.engines);
         for (uint32_t e = 0; e < pl.engines; e++) { hp.push_back(&sh.saved[e]); std::lock_guard<std::mutex> lk(*sh.reseed_m[e]); rs[e] = sh.reseed[e]; }
         if (!write_work(p.work_path, p.work_tmp, h, entries, hp, rs, keys)) fprintf(stderr, "WARNING: cannot write %s\n", p.work_path.c_str());
+        return true;
     };
     // the collector: every engine's records into the mode's one table
     std::atomic<bool> engines_done{false};
@@ -384,6 +409,7 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
             // -wt: every engine parks between two launches with its herd downloaded and its last records queued; the collector empties the queue; then
             // table, counters, stream, herds and re-seed lists belong to one moment of the search
             const auto ts = Clock::now();
+            { std::lock_guard<std::mutex> lk(sh.save_m); sh.barrier.open(); }
             sh.save_req = true;
             {
                 std::unique_lock<std::mutex> lk(sh.save_m);
@@ -395,7 +421,7 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
             }
             bool all_parked;
             { std::lock_guard<std::mutex> lk(sh.save_m); all_parked = sh.parked == pl.engines; }
-            if (all_parked && !sh.stop.load()) { write_state(); printf("\n[save] %s in %.2fs\n", p.work_path.c_str(), since(ts)); }
+            if (all_parked && !sh.stop.load() && write_state()) printf("\n[save] %s in %.2fs\n", p.work_path.c_str(), since(ts));
             { std::lock_guard<std::mutex> lk(sh.save_m); sh.save_req = false; }
             sh.save_cv.notify_all();
             last_save = Clock::now();
@@ -413,6 +439,6 @@ Outcome kang::run(const KangConfig &c, Prologue &p, Shared &sh, Mode &mode)
     if (mode.done()) { if (mode.saves) remove(p.work_path.c_str()); return DONE; }     // a stale file never outlives its job
     bool have = true;
     for (uint32_t e = 0; e < pl.engines; e++) have = have && sh.saved[e].size() == pl.kn;
-    if (have && mode.saves) write_state();                                           // engines joined, queue drained: the state is final
+    if (have && mode.saves && !write_state()) die("-kangaroo -kdpshard: the last save was refused, routed records never reached their table");      // engines joined, queue drained: the state is final
     return gave_up ? GAVE_UP : interrupted ? INTERRUPTED : c.ksteps && sh.steps.load() >= c.ksteps ? BUDGET : ENDED;
 }

@@ -34,6 +34,25 @@ struct Prologue {
     uint64_t rng;                                  // the seeded stream behind the jump table (-wl: the file's)
 };
 
+// -kdpshard: the barrier in front of an engine's last drain before a save ("a save stays a consistent cut").  Two kinds of round.  A SAVE round
+// is opened by the saver before it asks for a save; its count belongs to that round alone, and an engine that waits in it leaves it -- without draining,
+// nothing is saved from it -- when the round is given up (the request withdrawn, a stop, a newer round): a stop then brings the STOP round, the last one,
+// whose count is never reset and which every living engine enters once.  Plain data under Shared::save_m; -selftest kangaroo-barrier scripts it.
+struct SaveBarrier {
+    uint64_t round = 0;
+    uint32_t at_save = 0, at_stop = 0;
+    enum State { WAIT, ALL, GIVEN_UP };
+    void open() { round++; at_save = 0; }                                           // the saver, before save_req is set
+    uint64_t arrive(bool stopped) { if (stopped) at_stop++; else at_save++; return round; }
+    // stopped: the engine arrived in the stop round; my_round: what arrive() returned; living: engine threads alive; save_req, stop: as they stand now
+    State state(bool stopped, uint64_t my_round, uint32_t living, bool save_req, bool stop) const
+    {
+        if (stopped) return at_stop >= living ? ALL : WAIT;
+        if (round == my_round && at_save >= living) return ALL;
+        return round != my_round || !save_req || stop ? GIVEN_UP : WAIT;
+    }
+};
+
 // what the engines, the collector, the saver and the mode share
 struct Shared {
     explicit Shared(const Prologue &p);
@@ -57,6 +76,13 @@ struct Shared {
     uint32_t parked = 0, running = 0;              // (under save_m) engines waiting for the save to end / engine threads alive
     std::vector<std::vector<bsgs_kangaroo_state>> saved;      // per engine: the herd as downloaded at the last park or at the end
     Clock::time_point ended;                       // when the engines and the collector had ended, before the last save
+    // -kdpshard ("divided over engines"): what other engines routed to engine e waits in inbox[e] until e inserts it before its next launch;
+    // routed[e]: records engine e sent away; barrier (under save_m): which engines have made their last launch before a save and pushed what it routed
+    struct Inbox { std::mutex m; std::vector<bsgs_kangaroo_record> recs; };
+    std::vector<std::unique_ptr<Inbox>> inbox;
+    std::unique_ptr<std::atomic<uint64_t>[]> routed;
+    SaveBarrier barrier;
+    bool inboxes_empty() { for (auto &b : inbox) { std::lock_guard<std::mutex> lk(b->m); if (!b->recs.empty()) return false; } return true; }
     void push_reseed(uint32_t e, uint32_t i) { std::lock_guard<std::mutex> lk(*reseed_m[e]); reseed[e].push_back(i); }
 };
 
@@ -78,6 +104,12 @@ public:
     // records that come back; the launch is kept so short that the records it is expected to write fill at most half of the largest record buffer, and when
     // the floor of the launch length does not do it, dp is raised as long as the command line (or a work file) has not fixed it
     bool counts_records = true, bound_launch = false, dp_free = false;
+    // a mode whose table in device memory is divided over the engines (-kdpshard): an engine drains its inbox before every launch, and before a save no
+    // engine drains its last inbox until every living engine has made its last launch (the barrier of the run loop)
+    bool sharded = false;
+    virtual std::string drain(bsgs_dev *dev, uint32_t e, Shared &sh) { (void)dev; (void)e; (void)sh; return ""; }
+    // once the device list stands (p.gpus) and before the herd is planned: a mode whose dp depends on the number of engines fixes it here
+    virtual void engines_known(Prologue &p) { (void)p; }
     const char *herd_label = "herds (GPU), engine ";                  // the [startup] line of a herd seeded in its engine's thread
     virtual std::string fingerprint(const Prologue &p, const WorkHeader &h) const = 0;
     // between the work file and the devices: the mode's own resume checks ("Recovery file was made with other settings"), its header fields, its first
@@ -87,6 +119,7 @@ public:
     virtual void planned(const Prologue &p) { (void)p; }
     // in an engine's thread; nullptr, or the name of the call that failed
     virtual const char *setup(bsgs_dev *dev) = 0;
+    virtual const char *setup_engine(bsgs_dev *dev, uint32_t e) { (void)e; return setup(dev); }      // ... for a mode that needs the engine's number
     // starts the kangaroos idx of engine e (empty: the whole herd, from the offsets drawn in engine order before the run); draws under the locks it needs
     virtual const char *seed(bsgs_dev *dev, uint32_t e, const std::vector<uint32_t> &idx, Shared &sh) = 0;
     // under sh.tab_m.  One record of engine e into the table: kangaroos to start afresh go on sh's lists, a finished search sets sh.stop; false: the rest of

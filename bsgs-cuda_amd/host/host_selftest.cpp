@@ -143,6 +143,12 @@ int selftest(int argc, char **argv)
             return kangaroo_dpkeys_plan_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-dpkeys") {                             // the hand-back rule of -kdpkeys on scripted records and pairs (no GPU)
             return kangaroo_dpkeys_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-barrier") {                            // -kdpshard's barrier before a save on scripted events (no GPU, no threads)
+            return kangaroo_barrier_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-dpshard-plan") {                       // the plan of -kdpshard for E engines (no GPU)
+            return kangaroo_dpshard_plan_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
+        } else if (a[i] == "kangaroo-dpshard") {                            // the hand-back rule of -kdpshard on scripted records with global ids (no GPU)
+            return kangaroo_dpshard_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-dpdev-plan") {                         // the plan of -kdpdev from the range width (no GPU)
             return kangaroo_dpdev_plan_selftest(std::vector<std::string>(a.begin() + (long)i + 1, a.end()));
         } else if (a[i] == "kangaroo-dpdev") {                              // the hand-back rule of -kdpdev on scripted records and pairs (no GPU)

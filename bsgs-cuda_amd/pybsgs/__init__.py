@@ -34,6 +34,7 @@ NATIVE_SYMBOLS = [
     "bsgs_kangaroo_tames_gen_load", "bsgs_kangaroo_tames_gen_read_sorted",
     "bsgs_kangaroo_dptable_begin", "bsgs_kangaroo_run_dptable", "bsgs_kangaroo_dptable_insert", "bsgs_kangaroo_dptable_load", "bsgs_kangaroo_dptable_read", "bsgs_kangaroo_dptable_end",
     "bsgs_kangaroo_dptable_begin_keys", "bsgs_kangaroo_run_dptable_keys", "bsgs_kangaroo_dptable_insert_keys",
+    "bsgs_kangaroo_dptable_begin_shard", "bsgs_kangaroo_run_dptable_shard", "bsgs_kangaroo_dptable_insert_shard",
 ]
 # exported by the TEST build only (build/libbsgs_hip_test.so = the shipped objects + csrc/test_hooks.hip; include/bsgs_hip.h under BSGS_TEST_HOOKS)
 TEST_HOOK_SYMBOLS = ["bsgs_debug_corrupt_table", "bsgs_debug_realloc", "bsgs_debug_launch_split", "bsgs_debug_last_split"]
@@ -82,6 +83,7 @@ KANGAROO_NEG, KANGAROO_CYCLE = 2, 4                # the symmetric walk (kangaro
 KANGAROO_GEN_DEAD, KANGAROO_GEN_DUPLICATE, KANGAROO_GEN_TAG_ZERO, KANGAROO_GEN_FULL = range(4)   # why the growing tame table hands a record back
 KANGAROO_DPT_DEAD, KANGAROO_DPT_DUPLICATE, KANGAROO_DPT_TAG_ZERO, KANGAROO_DPT_FULL, KANGAROO_DPT_STORED = range(5)   # the distinguished-point table's hand-backs
 KANGAROO_DPT_KEY_SHIFT = 8   # the table for a key list: a hand-back's `reserved` = reason | key << 8; an entry's owner: 0 tame, 1 + key wild, bit 31 NEG
+KANGAROO_DPT_MAX_SHARDS = 16   # the table divided over engines: shard(tag) = ((tag >> 48) * shards) >> 16
 KANGAROO_KEY_SHIFT, KANGAROO_MAX_KEYS = 8, 65535   # many keys in one herd (kangaroo_set_keys): a wild kangaroo's key index, 16 bits of its flags
 
 _lib = None
@@ -223,6 +225,11 @@ def lib():
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
             "bsgs_kangaroo_dptable_insert_keys": [vp, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32),
                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+            "bsgs_kangaroo_dptable_begin_shard": [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32],
+            "bsgs_kangaroo_run_dptable_shard": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(KangarooRecord), C.c_uint32,
+                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)],
+            "bsgs_kangaroo_dptable_insert_shard": [vp, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32),
+                                                   C.POINTER(KangarooRecord), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
             "bsgs_kangaroo_run_tames_keys": [vp, C.c_uint32, C.POINTER(KangarooRecord), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_float)],
         }
@@ -330,6 +337,7 @@ class Device:
         self.L = lib()
         self._kang_keyed = False               # the herd is one of kangaroo_setup_sym_keys: states carry a key
         self._kang_cap = 0                     # record capacity of the herd (kangaroo_setup*)
+        self._dpt_shards = 1                   # shards of the table begun by kangaroo_dptable_begin_shard
 
     def close(self):
         if self.h:
@@ -1032,6 +1040,57 @@ class Device:
         out = (KangarooRecord * max(1, cap))()
         _chk(self.L.bsgs_kangaroo_dptable_insert_keys(self.h, arr, m, out, cap, C.byref(n), C.byref(entries), C.byref(dropped)))
         return self._keys_handed_back(out, n.value), entries.value, dropped.value
+
+    # ---- the distinguished-point table divided over engines (include/bsgs_hip.h "Kangaroo, distinguished-point table divided over engines")
+    def kangaroo_dptable_begin_shard(self, capacity, shard, shards, kangaroo_base=0):
+        """allocates shard `shard` of a table of `shards` shards, `capacity` entries here, under the herd of kangaroo_setup / kangaroo_setup_sym; the herd's
+        kangaroos are kangaroo_base + index wherever a record leaves the device"""
+        _chk(self.L.bsgs_kangaroo_dptable_begin_shard(self.h, capacity, shard, shards, kangaroo_base))
+        self._dpt_shards = shards
+
+    def _routed_groups(self, recs, buf, counts, raw):
+        """the routed records as one group per shard, in the shards' order: bytes (raw) or hand-back style records with `reserved` as "reason" """
+        out, at = [], 0
+        for c in counts:
+            out.append(buf.raw[64 * at:64 * (at + c)] if raw else self._gen_handed_back(recs[at:at + c], c))
+            at += c
+        return out
+
+    def kangaroo_run_dptable_shard(self, steps, max_recs=None, max_routed=None, raw=False):
+        """kangaroo_run_dptable on a sharded table: (hand-backs, routed, n_seen, n_entries, dropped, kernel ms); routed = one group of records per shard
+        (the own shard's empty), every id global; raw: bytes in the place of the lists"""
+        cap = 2 * self._kang_cap if max_recs is None else max_recs
+        rcap = self._kang_cap if max_routed is None else max_routed
+        n, seen, entries, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        counts = (C.c_uint32 * KANGAROO_DPT_MAX_SHARDS)()
+        recs, buf = self._raw_records_out(cap)
+        routed, rbuf = self._raw_records_out(rcap)
+        _chk(self.L.bsgs_kangaroo_run_dptable_shard(self.h, steps, recs, cap, C.byref(n), routed, rcap, counts, C.byref(seen), C.byref(entries), C.byref(dropped),
+                                                    C.byref(ms)))
+        groups = self._routed_groups(routed, rbuf, list(counts)[:self._dpt_shards], raw)
+        return (buf.raw[:64 * n.value] if raw else self._gen_handed_back(recs, n.value)), groups, seen.value, entries.value, dropped.value, ms.value
+
+    def kangaroo_dptable_insert_shard(self, records, max_recs=None, max_routed=None, raw=False):
+        """insert with routing and resolve alone on records of the caller's, (tag or x, d, flags, kangaroo) each, their ids global: (hand-backs, routed,
+        n_entries, dropped); raw: records = the bytes of 64-byte records, and bytes come back"""
+        if raw:
+            arr, m, keep = self._raw_records_in(records)
+        else:
+            m = len(records)
+            arr = (KangarooRecord * max(1, m))()
+            for k, (x, d, fl, kang) in enumerate(records):
+                arr[k].x[:] = le32(x)
+                arr[k].d[:] = (d % (1 << 128)).to_bytes(16, "little")
+                arr[k].flags, arr[k].kangaroo = fl, kang
+        cap = 2 * self._kang_cap if max_recs is None else max_recs
+        rcap = self._kang_cap if max_routed is None else max_routed
+        n, entries, dropped = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        counts = (C.c_uint32 * KANGAROO_DPT_MAX_SHARDS)()
+        out, buf = self._raw_records_out(cap)
+        routed, rbuf = self._raw_records_out(rcap)
+        _chk(self.L.bsgs_kangaroo_dptable_insert_shard(self.h, arr, m, out, cap, C.byref(n), routed, rcap, counts, C.byref(entries), C.byref(dropped)))
+        groups = self._routed_groups(routed, rbuf, list(counts)[:self._dpt_shards], raw)
+        return (buf.raw[:64 * n.value] if raw else self._gen_handed_back(out, n.value)), groups, entries.value, dropped.value
 
     def kangaroo_seed(self, Q, offsets, flags, first=0, idx=None):
         """start points on the GPU: kangaroo idx[k] (first + k without idx) := (d*G or Q + d*G, d, flags[k]) for d = offsets[k] (a signed integer) and

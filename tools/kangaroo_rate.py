@@ -2,7 +2,7 @@
 """Kangaroo walk rate on one GPU: a full herd (16 kangaroos per thread, four waves per SIMD on every CU) at seeded starts, warm-up launches, then timed
 launches between device synchronisations.  Prints one JSON line: steps/s, ms per launch, bytes per step from the layout, the kernel's VGPR count.
 
-    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--dptable N [--keys]] [--no-vgprs] [--out FILE]
+    tools/kangaroo_rate.py [--steps 256] [--launches 8] [--warmup 2] [--dp 16] [--per-thread 16] [--sym [--jumps 1024] [--keys]] [--tames N] [--tamesgen N] [--dptable N [--keys]] [--dpshard E] [--no-vgprs] [--out FILE]
     tools/kangaroo_rate.py --tamesload N | --tamessort N [--reps 3] [--out FILE]
 
 --sym times the symmetric walk (bsgs_kangaroo_setup_sym: the negation map, its jump table in device memory, the cycle check of every launch); with --keys
@@ -23,6 +23,12 @@ writes at most 2^22 records (a full herd at --dp 7: --steps 64).  With --keys th
 bsgs_kangaroo_run_dptable_keys: the search of -infile -kdpkeys) under a herd that serves 16 keys -- that of bsgs_kangaroo_setup with a key list, or with
 --sym that of bsgs_kangaroo_setup_sym_keys -- seeded by bsgs_kangaroo_seed_keys, the wild half dealt out over the keys: the walk alone and walk + keyed
 insert + resolve, alternating in one process.
+
+--dpshard E (plain walk or --sym) opens TWO engines on the one GPU, each with a full herd of the same starts and a table of 2^27 entries: one begun by
+bsgs_kangaroo_dptable_begin, one by bsgs_kangaroo_dptable_begin_shard as shard 0 of E.  Launch by launch, in one process, it times bsgs_kangaroo_run_dptable
+(the --dptable leg) against bsgs_kangaroo_run_dptable_shard, which routes (E - 1) / E of its records out, followed by what an engine of a sharded search does
+with its inbox: bsgs_kangaroo_dptable_insert_shard of as many records as were routed, the routed ones themselves with their shard bits rewritten to this
+shard's (wall time: upload, insert, resolve).  Reports ms per launch of each and the bytes relayed.
 
 --tamesload N times bsgs_kangaroo_tames_gen_load of N synthetic entries (pairwise different tags, 24 bytes each from pageable host memory) into a fresh growing
 table of capacity N, --reps times.  --tamessort N loads such a table once and times bsgs_kangaroo_tames_gen_read_sorted of all N entries (harvest, radix sort,
@@ -121,6 +127,86 @@ def table_legs(a):
     dev.close()
 
 
+def shard_legs(a):
+    """--dpshard E: the unsharded and the sharded table under the same walk, on two engines of one GPU, alternating"""
+    import numpy as np
+    REC = np.dtype([("x", "<u8", (4,)), ("d", "<u8", (2,)), ("kangaroo", "<u4"), ("flags", "<u4"), ("step", "<u4"), ("reserved", "<u4")])
+    E, cap, capacity = a.dpshard, 1 << 22, 1 << 27
+    devs = [pybsgs.Device(0), pybsgs.Device(0)]
+    L = devs[0].L
+    cus = C.c_int()
+    pybsgs._chk(L.bsgs_dev_cu_count(devs[0].h, C.byref(cus)))
+    n = cus.value * 1024 * a.per_thread
+    scal = [splitmix64(j)[1] % (1 << 62) + 1 for j in range(a.jumps if a.sym else 64)]
+    jumps = [mul(s) for s in scal]
+    d = np.random.RandomState(7).randint(1, 1 << 62, size=(n, 2), dtype=np.uint64)
+    d[:, 1] &= np.uint64((1 << 36) - 1)                              # offsets below 2^100, pairwise different but for a 2^-62 chance
+    flags = (C.c_uint32 * n)(*([0] * (n // 2) + [pybsgs.KANGAROO_WILD] * (n - n // 2)))
+    q = mul(0xD15C0 << 70)
+    begin_s = []
+    for k, dev in enumerate(devs):
+        (dev.kangaroo_setup_sym if a.sym else dev.kangaroo_setup)(jumps, scal, a.dp, n, a.per_thread, cap)
+        pybsgs._chk(L.bsgs_kangaroo_seed(dev.h, pybsgs.le32(q[0]) + pybsgs.le32(q[1]), None, 0, n, d.tobytes(), flags, None, None))
+        t0 = time.perf_counter()
+        if k == 0:
+            dev.kangaroo_dptable_begin(capacity)
+        else:
+            dev.kangaroo_dptable_begin_shard(capacity, 0, E, 0)
+        begin_s.append(time.perf_counter() - t0)
+    recs, routed = (pybsgs.KangarooRecord * (2 * cap))(), np.zeros(cap, REC)
+    back = (pybsgs.KangarooRecord * (2 * cap))()
+    cnt, seen, n_entries, dropped, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+    counts = (C.c_uint32 * 16)()
+    rp = routed.ctypes.data_as(C.POINTER(pybsgs.KangarooRecord))
+
+    def launch_one():
+        pybsgs._chk(L.bsgs_kangaroo_run_dptable(devs[0].h, a.steps, recs, 2 * cap, C.byref(cnt), C.byref(seen), C.byref(n_entries), C.byref(dropped), C.byref(ms)))
+        return ms.value, seen.value, dropped.value
+
+    def launch_shard():
+        pybsgs._chk(L.bsgs_kangaroo_run_dptable_shard(devs[1].h, a.steps, recs, 2 * cap, C.byref(cnt), rp, cap, counts, C.byref(seen), C.byref(n_entries), C.byref(dropped),
+                                                      C.byref(ms)))
+        kernel, total, dr, m = ms.value, seen.value, dropped.value, sum(counts)
+        # the inbox of a sharded search: as many records as went out, bound for this shard.  The routed records with their shard bits divided by E name shard 0
+        routed["x"][:m, 0] = (routed["x"][:m, 0] & np.uint64((1 << 48) - 1)) | ((routed["x"][:m, 0] >> np.uint64(48)) // np.uint64(E) << np.uint64(48))
+        t0 = time.perf_counter()
+        pybsgs._chk(L.bsgs_kangaroo_dptable_insert_shard(devs[1].h, rp, m, back, 2 * cap, C.byref(cnt), None, 0, counts, C.byref(n_entries), C.byref(dropped)))
+        inbox = (time.perf_counter() - t0) * 1e3
+        assert sum(counts) == 0, "an inbox record was routed again"
+        return kernel, inbox, total, m, dr + dropped.value
+
+    for _ in range(a.warmup):
+        launch_one()
+        launch_shard()
+    one, shard, inbox, nrec, nrouted, dr = [], [], [], 0, 0, 0
+    for _ in range(a.launches):
+        k, r, x = launch_one()
+        one.append(k)
+        dr += x
+        k, i, r, m, x = launch_shard()
+        shard.append(k)
+        inbox.append(i)
+        nrec += r
+        nrouted += m
+        dr += x
+    mean = lambda v: sum(v) / len(v)
+    res = {"what": "kangaroo walk with the distinguished-point table in device memory: one table against shard 0 of %d with its inbox, two engines on one GPU, full herds, half tame "
+                   "half wild" % E + (", symmetric walk" if a.sym else ""),
+           "gpu": devs[0].name(), "shards": E, "kangaroos": n, "per_thread": a.per_thread, "steps_per_launch": a.steps, "dp": a.dp, "launches": a.launches, "capacity": capacity,
+           "begin_s": begin_s, "ms_per_launch_walk_insert_resolve": mean(one), "ms_per_launch_walk_shard_insert_scatter_resolve": mean(shard), "ms_inbox_insert_wall": mean(inbox),
+           "ms_shard_minus_one": mean(shard) - mean(one), "ms_one_each": one, "ms_shard_each": shard, "ms_inbox_each": inbox,
+           "records_per_launch": nrec / a.launches, "records_routed_per_launch": nrouted / a.launches, "routed_share": nrouted / max(1, nrec),
+           "bytes_relayed_per_launch": 2 * 64 * nrouted / a.launches, "dropped": dr,
+           "steps_per_s_kernel_one": n * a.steps / (mean(one) / 1e3), "steps_per_s_shard_with_inbox": n * a.steps / ((mean(shard) + mean(inbox)) / 1e3)}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    for dev in devs:
+        dev.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=256)
@@ -134,6 +220,7 @@ def main():
     ap.add_argument("--tames", type=int, default=0)
     ap.add_argument("--tamesgen", type=int, default=0)
     ap.add_argument("--dptable", type=int, default=0)
+    ap.add_argument("--dpshard", type=int, default=0)
     ap.add_argument("--tamesload", type=int, default=0)
     ap.add_argument("--tamessort", type=int, default=0)
     ap.add_argument("--reps", type=int, default=3)
@@ -146,8 +233,12 @@ def main():
         ap.error("--tamesgen goes with the plain walk or --sym alone")
     if a.dptable and (a.tames or a.tamesgen):
         ap.error("--dptable goes with the plain walk or --sym, alone or with --keys")
+    if a.dpshard and (a.keys or a.tames or a.tamesgen or a.dptable or not 1 <= a.dpshard <= pybsgs.KANGAROO_DPT_MAX_SHARDS):
+        ap.error("--dpshard 1..16 goes with the plain walk or --sym alone")
     if a.tamesload or a.tamessort:
         return table_legs(a)
+    if a.dpshard:
+        return shard_legs(a)
     dev = pybsgs.Device(0)
     L = dev.L
     cus = C.c_int()
